@@ -2,19 +2,25 @@
 """Benchmark of the Free Hunch hot path on MI355X (contract: see the task statement / DESIGN.md "Measurement").
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--arch ffhq|imagenet] [--operator NAME]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one batch of B independent 256x256 images, each taken through the full FH-Heun sampler
 (num_steps = 30 -> 59 guidance calls = 59 UNet forwards + 59 input-VJPs + 59 CG solves + covariance updates).
 Workload at N = 1: BASELINE.json configs[1] (FFHQ-256 architecture, gaussian_blur, low-rank covariance,
 num_steps = 30, batch = 8).  N > 1: one process per GPU (torch.distributed / RCCL), every rank runs its own batch
 (weak scaling), outputs are exchanged with ONE all_gather per step inside the timed region.
-Inputs are synthetic (seeded images and weights; there are no checkpoints or datasets offline).
+Inputs are synthetic (seeded images and weights; there are no checkpoints or datasets offline): the same arguments
+give the same inputs in every run.
 
-Besides the headline line the JSON carries
-  roofline      cov-apply (fh_rep_apply at d = 196608, m = 32) timed with events on the launch stream,
-                algorithmic bytes / time against the 8 TB/s HBM peak
-  cpu_baseline  the CPU oracle (a port of the reference path) timed on the host cores on a bounded sample of the
-                same workload (the first guidance calls of one image), extrapolated to images/s
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR writes the images of the last timed step (every rank's, in rank order) to DIR/images.npy as float32
+[N * B, 3, 256, 256] (0..255), so that two builds can be compared output for output.
+--full adds the legs beside the headline (each a measurement of its own, after the timed steps):
+  roofline*        cov-apply (fh_rep_apply at d = 196608, m = 32), the dominant UNet convolution and the dense
+                   covariance kernels, timed with events on the launch stream against the HBM / MFMA peaks
+  half_split_mode  the same workload with --unet-dtype fp16x3 (N = 1, fp32 runs; --no-half-split-leg skips it)
+  cpu_baseline     the CPU oracle (a port of the reference path) timed on the host cores on a bounded sample of the
+                   same workload, extrapolated to images/s (N = 1; --no-cpu-baseline skips it)
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
 
 
 def smooth_images(n, size, seed):
@@ -493,6 +500,19 @@ def run_steps(step, steps, warmup, world, coll, device_sync):
     return elapsed
 
 
+def dump_outputs(out_dir, images_u8):
+    """DIR/images.npy: the images of the last timed step as float32.  Beyond 64 MB a fixed (seeded) sample of the images,
+    with their indices in DIR/images_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = images_u8.numpy().astype(np.float32)
+    per_image = x[0].nbytes
+    if x.nbytes > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(x), DUMP_LIMIT_BYTES // per_image, replace=False))
+        x = x[keep]
+        np.save(os.path.join(out_dir, "images_index.npy"), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, "images.npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -509,11 +529,19 @@ def main():
     ap.add_argument("--unet-backend", default=os.environ.get("FH_UNET_BACKEND", "hip"))
     ap.add_argument("--unet-dtype", default="fp32", choices=["fp32", "fp16x3", "bf16x3", "bf16", "fp16"],
                     help="bf16: reduced-precision torso (non-parity speed mode, reported separately from the fp32 headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step as DIR/images.npy (float32; at most 64 MB: a fixed sample "
+                         "of the images beyond that, their indices in DIR/images_index.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run the roofline, half-split and CPU-baseline legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
     ap.add_argument("--no-half-split-leg", action="store_true",
-                    help="skip the extra leg that times the same workload with --unet-dtype fp16x3 (N = 1, fp32 runs only)")
+                    help="with --full: skip the extra leg that times the same workload with --unet-dtype fp16x3 "
+                         "(N = 1, fp32 runs only)")
     ap.add_argument("--cpu-calls", type=int, default=2, help="real UNet calls timed by the CPU-baseline leg")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher.  Nothing above has touched the GPU (importing torch
@@ -548,14 +576,19 @@ def main():
     data_dir = os.path.join(ROOT, "free-hunch_amd", "data")
     net, cfg = build_net(a.arch, device, a.unet_backend, a.unet_dtype)
     images = smooth_images(a.batch, 256, 1234 + rank)
+    last = {}
 
     def step(i):
         seeds = [(i * world + rank) * a.batch + j for j in range(a.batch)]
         out = run_batch(net, images, seeds, a.operator, a.num_steps, a.solver, device, data_dir, a.groups)
-        exchange(out, world, coll)
+        last["gathered"] = exchange(out, world, coll)  # what a caller of the step receives: every rank's images
         return out
 
     elapsed = run_steps(step, a.steps, a.warmup, world, coll, torch.cuda.synchronize)
+
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, torch.cat([t.cpu() for t in last["gathered"]], 0))
+    last.clear()
 
     if rank == 0:
         total_images = a.steps * a.batch * world
@@ -582,34 +615,35 @@ def main():
                        "net_calls_per_image": 2 * a.num_steps - 1 if a.solver == "heun" else a.num_steps,
                        "cg_iters_per_image_last_step": getattr(run_batch, "cg_iters", None)},
         }
-        # headline point of SURVEY.md 8(d): d = 196608, m = 32, b = the batch the lock-step CG applies per launch
-        line["roofline"] = roofline_cov_apply(device, nimg=min(a.batch, 8), iters=100)
-        if a.batch > 1:
-            line["roofline_cov_apply_b1"] = roofline_cov_apply(device, nimg=1)
-        line["roofline_unet_conv"] = roofline_conv_mfma(device)
-        line["roofline_dense_cov_apply"] = roofline_dense_cov_apply(device)
-        if world == 1 and a.unet_dtype == "fp32" and a.unet_backend == "hip" and not a.no_half_split_leg:
-            # The same workload once more with the opt-in half-split convolutions, measured in the same
-            # process on the same box, so that the two figures can be compared without the box-to-box spread.  Reported
-            # beside the headline, never as `value`.
-            del net
-            net2, _ = build_net(a.arch, device, a.unet_backend, "fp16x3")
-            k = max(1, min(a.steps, 3))
+        if a.full:  # the measurements beside the headline, after the timed steps
+            # headline point of SURVEY.md 8(d): d = 196608, m = 32, b = the batch the lock-step CG applies per launch
+            line["roofline"] = roofline_cov_apply(device, nimg=min(a.batch, 8), iters=100)
+            if a.batch > 1:
+                line["roofline_cov_apply_b1"] = roofline_cov_apply(device, nimg=1)
+            line["roofline_unet_conv"] = roofline_conv_mfma(device)
+            line["roofline_dense_cov_apply"] = roofline_dense_cov_apply(device)
+            if world == 1 and a.unet_dtype == "fp32" and a.unet_backend == "hip" and not a.no_half_split_leg:
+                # The same workload once more with the opt-in half-split convolutions, measured in the same
+                # process on the same box, so that the two figures can be compared without the box-to-box spread.  Reported
+                # beside the headline, never as `value`.
+                del net
+                net2, _ = build_net(a.arch, device, a.unet_backend, "fp16x3")
+                k = max(1, min(a.steps, 3))
 
-            def step2(i):
-                seeds = [i * a.batch + j for j in range(a.batch)]
-                return run_batch(net2, images, seeds, a.operator, a.num_steps, a.solver, device, data_dir, a.groups)
+                def step2(i):
+                    seeds = [i * a.batch + j for j in range(a.batch)]
+                    return run_batch(net2, images, seeds, a.operator, a.num_steps, a.solver, device, data_dir, a.groups)
 
-            t2 = run_steps(step2, k, 1, 1, coll, torch.cuda.synchronize)
-            line["half_split_mode"] = {
-                "value": round(k * a.batch / t2, 5), "unit": "images/s", "steps": k, "warmup": 1,
-                "ms_per_step": round(t2 / k * 1e3, 2), "flag": "--unet-dtype fp16x3",
-                "dtype": "f32 UNet with the 3x3 convolutions as 3 half-precision products of 2-plane operands, fp32 accumulation "
-                         "(fp32-convolution accuracy against float64: tests/test_hip_unet.py::test_half_split_*; not "
-                         "bit-comparable with the exact split, hence opt-in) + f64 covariance/CG"}
-            del net2
-        if world == 1 and not a.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(a.arch, a.operator, a.num_steps, data_dir, a.cpu_calls, a.solver)
+                t2 = run_steps(step2, k, 1, 1, coll, torch.cuda.synchronize)
+                line["half_split_mode"] = {
+                    "value": round(k * a.batch / t2, 5), "unit": "images/s", "steps": k, "warmup": 1,
+                    "ms_per_step": round(t2 / k * 1e3, 2), "flag": "--unet-dtype fp16x3",
+                    "dtype": "f32 UNet with the 3x3 convolutions as 3 half-precision products of 2-plane operands, fp32 accumulation "
+                             "(fp32-convolution accuracy against float64: tests/test_hip_unet.py::test_half_split_*; not "
+                             "bit-comparable with the exact split, hence opt-in) + f64 covariance/CG"}
+                del net2
+            if world == 1 and not a.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(a.arch, a.operator, a.num_steps, data_dir, a.cpu_calls, a.solver)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
