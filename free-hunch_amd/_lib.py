@@ -56,6 +56,7 @@ _SIGS = {
     "fh_context_status": ([C.c_void_p, C.c_void_p], C.c_int),
     "fh_debug_read_stamps": ([C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p], C.c_int),
     "fh_dct2d": ([C.c_void_p, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_dct_moments_u8": ([C.c_void_p, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_rep_apply": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
     "fh_rep_apply_batched": ([C.c_void_p, C.POINTER(FhBatch), C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
     "fh_rep_invert": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_double, c_dp, c_dp, c_dp, C.c_int, C.c_int64, C.c_int,
@@ -204,6 +205,15 @@ class Context:
         planes = x.numel() // (self.S * self.S)
         check(self.lib.fh_dct2d(self.h, ptr(x), ptr(out), planes, int(inverse), stream()), "fh_dct2d")
         return out
+
+    def dct_moments_u8(self, imgs, work, sum_, sumsq):
+        """sum_ += dct2(x), sumsq += dct2(x)^2 over the uint8 images [n,3,S,S], x = u8 / 127.5 - 1; work: n*3*S*S doubles."""
+        n = imgs.shape[0]
+        assert imgs.dtype == torch.uint8 and tuple(imgs.shape[1:]) == (3, self.S, self.S)
+        assert work.dtype == sum_.dtype == sumsq.dtype == torch.float64
+        assert work.numel() >= imgs.numel() and sum_.numel() == sumsq.numel() == 3 * self.S * self.S
+        check(self.lib.fh_dct_moments_u8(self.h, ptr(imgs), n, ptr(work), ptr(sum_), ptr(sumsq), stream()),
+              "fh_dct_moments_u8")
 
     def rep_apply(self, D, r, B, M, z, out, m):
         check(self.lib.fh_rep_apply(self.h, ptr(D), ptr(r) if m else None, ptr(B) if m else None,

@@ -332,6 +332,38 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// DCT-variance prior (fh_dct_moments_u8): ingest and moments around the DCT passes.  Both are streaming kernels over a
+// few MB; the tool they serve is bound by image decoding, so nothing here goes beyond coalesced 16-byte accesses.
+// ------------------------------------------------------------------------------------------------
+// x = u8 / 127.5 - 1 over `quads` groups of four pixels: one 4-byte load, two 16-byte stores per thread
+__global__ __launch_bounds__(256) void k_u8_to_f64(const uint8_t* __restrict__ in, double* __restrict__ out, int64_t quads) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= quads) return;
+  const uchar4 u = reinterpret_cast<const uchar4*>(in)[q];
+  double2* o = reinterpret_cast<double2*>(out + 4 * q);
+  o[0] = make_double2((double)u.x / 127.5 - 1.0, (double)u.y / 127.5 - 1.0);
+  o[1] = make_double2((double)u.z / 127.5 - 1.0, (double)u.w / 127.5 - 1.0);
+}
+
+// sum[k] += z_i[k], sumsq[k] += z_i[k]^2 for i = 0 .. n-1 in index order, z [n][per].  One thread owns two coefficients
+// and carries both running sums in registers from the values already in `sum` / `sumsq`: no atomics, no reduction across
+// threads, so a coefficient sees the same chain of additions however the images were split into calls.
+__global__ __launch_bounds__(256) void k_dct_moments(const double* __restrict__ z, double* __restrict__ sum,
+                                                     double* __restrict__ sumsq, int per, int n) {
+  const int k = 2 * ((int)blockIdx.x * 256 + (int)threadIdx.x);
+  if (k >= per) return;  // per is even: k + 1 < per
+  double2 s = *reinterpret_cast<const double2*>(sum + k);
+  double2 q = *reinterpret_cast<const double2*>(sumsq + k);
+  for (int i = 0; i < n; ++i) {
+    const double2 v = *reinterpret_cast<const double2*>(z + (int64_t)i * per + k);
+    s.x += v.x, s.y += v.y;
+    q.x = fma(v.x, v.x, q.x), q.y = fma(v.y, v.y, q.y);
+  }
+  *reinterpret_cast<double2*>(sum + k) = s;
+  *reinterpret_cast<double2*>(sumsq + k) = q;
+}
+
 // Two dense S x S passes over `planes` images: T = X b_w^T (along W), out = b_h T (along H) [+ add_scale * add].
 // b_w = b_h = the DCT basis (or its transpose) gives the 2-D DCT-II / DCT-III; a separable blur folded into the bases
 // (fh_problem.fold_*) makes the same two passes compute dct2(A^T x) or A(idct2(x)).
@@ -2380,6 +2412,23 @@ int fh_context_status(fh_context* ctx, void* stream) {
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream) {
   if (!ctx || !in || !out || planes < 1) return FH_EINVAL;
   return dct2d_launch(ctx, in, out, planes, inverse, nullptr, (hipStream_t)stream);
+}
+
+int fh_dct_moments_u8(fh_context* ctx, const uint8_t* imgs, int n, double* work, double* sum, double* sumsq, void* stream) {
+  if (!ctx || !imgs || !work || !sum || !sumsq || n < 1) return FH_EINVAL;
+  if (((uintptr_t)imgs & 3) || (((uintptr_t)work | (uintptr_t)sum | (uintptr_t)sumsq) & 15)) return FH_EINVAL;  // vector accesses
+  if ((int64_t)3 * n > ctx->planes_max) return FH_ESIZE;
+  const hipStream_t st = (hipStream_t)stream;
+  const int per = 3 * ctx->S * ctx->S;  // S is even (fh_context_create): per % 4 == 0
+  const int64_t quads = (int64_t)n * per / 4;
+  hipLaunchKernelGGL(k_u8_to_f64, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, imgs, work, quads);
+  FH_LAUNCH_CHECK();
+  const int rc = dct2d_launch(ctx, work, work, 3 * n, 0, nullptr, st);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(k_dct_moments, dim3((unsigned)((per / 2 + 255) / 256)), dim3(256), 0, st, (const double*)work, sum, sumsq,
+                     per, n);
+  FH_LAUNCH_CHECK();
+  return 0;
 }
 
 int fh_rep_apply(fh_context* ctx, const double* D, const double* r, const double* B, const double* M, int ldm,

@@ -60,6 +60,10 @@ def main(argv=None):
     enc = StandardRGBEncoder()
     data_dir = o.dataset_path if os.path.exists(os.path.join(o.dataset_path, "dct_variance.pt")) else \
         os.path.join(ROOT, "free-hunch_amd", "data")
+    if rank == 0 and o.image_base_covariance == "dct_diagonal":
+        shipped = "" if data_dir == o.dataset_path else \
+            " (shipped ImageNet prior: python -m free_hunch_amd.frequency_analysis --data DIR builds the dataset's own)"
+        print(f"dct_variance: {os.path.join(data_dir, 'dct_variance.pt')}{shipped}", flush=True)
     # every option the reference forwards to its sampler / plugin (generate_conditional.py:121-130, 495)
     kw = dict(conditioning_mechanism=o.conditioning_mechanism, cond_scaling=o.cond_scaling, clip_x0_mean=o.clip_x0_mean,
               pigdm_posthoc_scaling=o.pigdm_posthoc_scaling, max_vector_count=o.max_vector_count, dataset_path=data_dir,

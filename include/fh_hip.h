@@ -58,6 +58,14 @@ int fh_debug_read_stamps(fh_context* ctx, unsigned long long* out_host, int coun
  * conditioning_utils/online_update_bfgs.py:351-374.  in may equal out. */
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream);
 
+/* Adds the DCT moments of n images to running sums: the accumulation loop of the DCT-variance prior,
+ * do_frequency_analysis.py:40-44.  imgs: uint8 [n][3][S][S] (4-byte aligned); work: n*3*S*S doubles of scratch;
+ * sum, sumsq: double [3][S][S], read and written (16-byte aligned, zeroed by the caller before the first call).
+ * x = u8/127.5 - 1, z = dct2(x) (orthonormal, the arithmetic of fh_dct2d), sum += z, sumsq += z*z, images added in
+ * index order by one thread per coefficient pair (no atomics): deterministic, and the sums after a set of images do
+ * not depend on how the set was split into calls.  3 * n must fit the context's planes_max (else FH_ESIZE). */
+int fh_dct_moments_u8(fh_context* ctx, const uint8_t* imgs, int n, double* work, double* sum, double* sumsq, void* stream);
+
 /* out = D.*z + r.*(B (M (B^T (r.*z))))   - one covariance/Hessian apply.
  * Replaces CovarianceHessianBFGS._denoiser_cov_vector_dot (and the three sibling *_vector_dot),
  * online_update_bfgs.py:194-231.  m may be 0 (then B, r, M may be null). */
