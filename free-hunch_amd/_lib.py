@@ -96,6 +96,7 @@ _SIGS = {
     "fh_groupnorm_bwd_apply_ex": ([c_dp] * 8 + [C.c_int, c_dp, c_dp, c_dp, c_dp] + [C.c_int] * 5 + [c_dp, C.c_void_p], C.c_int),
     "fh_conv2d_splitk": ([C.c_int] * 7, C.c_int),
     "fh_unet_set_precision": ([C.c_int], C.c_int),
+    "fh_unet_get_precision": ([], C.c_int),
     "fh_absmax_f32": ([c_dp, C.c_int64, c_dp, C.c_void_p], C.c_int),
     "fh_groupnorm_table": ([c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_conv2d_x6_norm_supported": ([C.c_int] * 5, C.c_int),
@@ -120,6 +121,11 @@ _SIGS = {
     "fh_add_f32": ([c_dp, c_dp, c_dp, C.c_int64, C.c_void_p], C.c_int),
     "fh_metrics_scratch_doubles": ([C.c_int] * 4, C.c_int64),
     "fh_metrics_u8": ([c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
+    "fh_lpips_prep_u8": ([c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_relu_f32": ([c_dp, C.c_int64, C.c_void_p], C.c_int),
+    "fh_relu_maxpool2_nhwc": ([c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_lpips_tap_scratch_doubles": ([C.c_int], C.c_int64),
+    "fh_lpips_tap": ([c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, c_dp, c_dp, C.c_int, C.c_void_p], C.c_int),
     "fh_cg_solve_batched": ([C.c_void_p, C.POINTER(FhProblem), C.POINTER(FhBatch), c_dp, c_dp, C.POINTER(C.c_double),
                              C.c_double, C.c_int, C.POINTER(FhCgInfo), C.c_void_p], C.c_int),
     "fh_cg_solve": ([C.c_void_p, C.POINTER(FhProblem), c_dp, c_dp, C.c_double, C.c_double, C.c_int,

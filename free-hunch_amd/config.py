@@ -43,6 +43,9 @@ SCHEMA = {
     # NEW: "fp32" | "bf16" | "fp16" - reduced-precision UNet torso (the reference's use_fp16 flag lives in the
     # checkpoint's setup file, training/openai_fp16_util.py:15-32); a non-parity speed mode
     "unet_dtype": (str, "fp32"),
+    # NEW: the two weight files of LPIPS-VGG (torchvision's vgg16-397923af.pth, lpips' weights/v0.1/vgg.pth); both empty =
+    # no LPIPS line in results.txt
+    "lpips_vgg_path": (str, ""), "lpips_lin_path": (str, ""),
 }
 
 
@@ -66,4 +69,6 @@ def load_config(argv=None):
         cfg[key] = _coerce(SCHEMA[key][0], value) if key in SCHEMA else value
     if cfg["outdir"] is None:
         raise SystemExit("--outdir=DIR is required")
+    if bool(cfg["lpips_vgg_path"]) != bool(cfg["lpips_lin_path"]):
+        raise SystemExit("--lpips_vgg_path and --lpips_lin_path go together: LPIPS needs both weight files")
     return SimpleNamespace(**cfg)

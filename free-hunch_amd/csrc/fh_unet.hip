@@ -1660,6 +1660,10 @@ int fh_unet_set_precision(int mode) {
   return 0;
 }
 
+int fh_unet_get_precision(void) {
+  return g_conv_np == 3 ? 0 : (g_conv_np == 1 ? 1 : (g_conv_np == 2 ? 2 : (g_conv_np == 16 ? 3 : 4)));
+}
+
 int fh_absmax_f32(const float* x, int64_t n, float* out, void* stream) {
   if (!out || n < 0 || (n > 0 && !x) || ((uintptr_t)x & 15)) return FH_EINVAL;
   hipStream_t st = (hipStream_t)stream;

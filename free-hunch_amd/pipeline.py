@@ -57,7 +57,7 @@ def metrics_u8(a, b):
     """(PSNR [N], SSIM [N]) float64 of uint8 image batches [N, C, H, W] on the device - the reference's per-image metrics
     (generate_conditional.py:543-551; skimage.metrics.structural_similarity(x, y, data_range=255, channel_axis=0): 7 x 7 uniform
     window, sample covariance, K1 = 0.01, K2 = 0.03, windows inside the image, mean over positions then channels), one
-    `fh_metrics_u8` call.  LPIPS needs a network download and is not offered.  scikit-image is absent from this image, so
+    `fh_metrics_u8` call.  LPIPS, the reference's third metric, is `lpips_u8` below.  scikit-image is absent from this image, so
     the kernel is pinned to a scipy.ndimage restatement of the published algorithm (tests/test_metrics.py), not to skimage
     itself: parity unpinned at that boundary."""
     from . import _lib
@@ -73,6 +73,17 @@ def metrics_u8(a, b):
     _lib.check(lib.fh_metrics_u8(a.data_ptr(), b.data_ptr(), N, C, H, W, scratch.data_ptr(), ssim.data_ptr(), psnr.data_ptr(),
                                  _lib.stream()), "fh_metrics_u8")
     return psnr, ssim
+
+
+def lpips_u8(a, b, model):
+    """LPIPS [N] float64 of uint8 image batches [N, 3, H, W] on the device (generate_conditional.py:499-583:
+    lpips.LPIPS(net='vgg') on (x / 255 - 0.5) * 2); `model` is a `free_hunch_amd.lpips.LPIPS` built from the two published weight
+    files.  Pinned to a PyTorch restatement of the published forward pass (tests/test_lpips_gpu.py), not to the lpips package,
+    which is absent from this image: parity unpinned at that boundary."""
+    from . import _lib
+    if not (a.is_cuda and b.is_cuda):
+        raise _lib.FhError("lpips_u8 runs on the device (libfh_hip.so); there is no CPU fallback")
+    return model(a, b)
 
 
 def psnr_u8(a, b):

@@ -97,7 +97,8 @@ assert CONV_MODE in ("x6", "wino", "f32"), CONV_MODE
 
 
 class _Conv:
-    def __init__(self, w, b):
+    def __init__(self, w, b, forward_only=False):
+        """forward_only: skip the input-gradient copies (wd, wu_d, wx_d stay None) for a network that is never differentiated"""
         co, ci = w.shape[0], w.shape[1]
         kh, kw = (w.shape[2], w.shape[3]) if w.dim() == 4 else (1, 1)  # conv1d qkv / proj_out are 1x1
         w4 = w.reshape(co, ci, kh, kw).float()
@@ -105,18 +106,20 @@ class _Conv:
         self.ci_p, self.co_p = _pad_to(ci, _K), _pad_to(co, _K)
         wf = torch.zeros(co, kh * kw, self.ci_p, dtype=torch.float32, device=w.device)
         wf[:, :, :ci] = w4.permute(0, 2, 3, 1).reshape(co, kh * kw, ci)
-        wd = torch.zeros(ci, kh * kw, self.co_p, dtype=torch.float32, device=w.device)
-        wd[:, :, :co] = w4.flip(2, 3).permute(1, 2, 3, 0).reshape(ci, kh * kw, co)
-        self.wf, self.wd, self.b = wf.contiguous(), wd.contiguous(), b.float().contiguous()
+        wd = None
+        if not forward_only:
+            wd = torch.zeros(ci, kh * kw, self.co_p, dtype=torch.float32, device=w.device)
+            wd[:, :, :co] = w4.flip(2, 3).permute(1, 2, 3, 0).reshape(ci, kh * kw, co).contiguous()
+        self.wf, self.wd, self.b = wf.contiguous(), wd, b.float().contiguous()
         # F(2,3) Winograd copies along kx, [4][rows][3 ky][K]: used for the large 3x3 layers (fh_conv3x3_wino_nhwc)
         self.wu_f = self.wu_d = self.wx_f = self.wx_d = None
         if kh == 3 and kw == 3 and CONV_MODE == "wino":
             self.wu_f = _wino(wf.reshape(co, 3, 3, self.ci_p))
-            self.wu_d = _wino(wd.reshape(ci, 3, 3, self.co_p))
+            self.wu_d = None if forward_only else _wino(wd.reshape(ci, 3, 3, self.co_p))
         self.wh_f = self.wh_d = None  # half-precision planes, built when the fp16 mode is first used
         self.ws_f = self.ws_d = None  # half-split planes (precision mode 4), built on first use
         if CONV_MODE == "x6":  # exact bf16 split of both copies (6 bytes per weight)
-            self.wx_f, self.wx_d = _split3(self.wf), _split3(self.wd)
+            self.wx_f, self.wx_d = _split3(self.wf), (None if forward_only else _split3(self.wd))
 
     def planes(self, fwd, mode):
         """the weight operand of the split-bf16 kernels for fh_unet_set_precision(mode): the three bf16 planes (modes 0-2),

@@ -7,7 +7,9 @@
 Same flags (free-hunch_amd/config.py), same outputs: DIR/images/{idx:06d}_{seed:06d}.png, cond_images/,
 forward_images/, results.txt.  Differences by design: images are sharded i -> rank i mod world with no per-image
 barrier, each rank runs `max_batch_size` images in lock-step, outputs are exchanged with one all_gather at the end,
-RNG is keyed by (seed, image index).  LPIPS needs a network download and is omitted; PSNR and SSIM are computed on device.
+RNG is keyed by (seed, image index).  PSNR, SSIM and LPIPS are computed on the device; LPIPS needs the two published weight
+files, which are not shipped: `--lpips_vgg_path=vgg16-397923af.pth --lpips_lin_path=weights/v0.1/vgg.pth` adds the `LPIPS:`
+line to results.txt, without them the run reports PSNR and SSIM only.
 `--synthetic_weights=ffhq|imagenet` runs with seeded random weights when no checkpoint is present."""
 import os
 import sys
@@ -24,11 +26,16 @@ def main(argv=None):
     from free_hunch_amd import unet as hu
     from free_hunch_amd.config import load_config
     from free_hunch_amd.measurements import get_operator
-    from free_hunch_amd.pipeline import gather_images, list_images, load_image_u8, metrics_u8, shard_indices
+    from free_hunch_amd.pipeline import gather_images, list_images, load_image_u8, lpips_u8, metrics_u8, shard_indices
     from free_hunch_amd.precond import iDDPMLinearPrecond
     from free_hunch_amd.sampler import StandardRGBEncoder, conditional_sampler, conditional_sampler_grouped
 
     o = load_config(argv)
+    # LPIPS weights are read before anything else happens: a wrong path must not cost a sampling run
+    lpips_state = None
+    if o.lpips_vgg_path:
+        from free_hunch_amd import lpips as fh_lpips
+        lpips_state = fh_lpips.load_weights(o.lpips_vgg_path, o.lpips_lin_path)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     from free_hunch_amd.conditioning_mechanisms import choose_conditioning_mechanism
@@ -50,6 +57,8 @@ def main(argv=None):
         model, cfg = hu.load_model(o.openai_state_dict_path, o.openai_setup_path, backend=o.unet_backend,
                                    dtype=None if o.unet_dtype == "fp32" else o.unet_dtype)
     net = iDDPMLinearPrecond(model.to(device).eval(), cfg.image_size, 3).to(device)
+    # the metric's network is packed now, not after sampling: a failure here must not cost the run
+    lpips_model = None if lpips_state is None else fh_lpips.LPIPS(lpips_state, device)
     S = cfg.image_size
 
     files = list_images(o.dataset_path)[: o.total_images]
@@ -121,12 +130,19 @@ def main(argv=None):
     unit_ids = [i * ns + o.seeds.index(sd) for i, sd in units]  # global position of (image, seed)
     # metrics as in generate_conditional.py:539-569: per image on the device (fh_metrics_u8); the partial sums travel in the
     # header of the ONE all_gather that collects the images (the reference: a barrier per image + three all_reduces)
-    sums = torch.zeros(3, dtype=torch.float64, device=device)
+    sums = torch.zeros(3 if lpips_state is None else 4, dtype=torch.float64, device=device)
     if local_out.shape[0]:
         ps, ss = metrics_u8(local_out, local_cond)
-        sums = torch.stack([ps.sum(), ss.sum(), torch.tensor(float(local_out.shape[0]), dtype=torch.float64, device=device)])
+        parts = [ps.sum(), ss.sum(), torch.tensor(float(local_out.shape[0]), dtype=torch.float64, device=device)]
+        if lpips_state is not None:  # fourth header element: the rank-local LPIPS sum
+            parts.append(lpips_u8(local_out, local_cond, lpips_model).sum())
+        sums = torch.stack(parts)
     all_out, sums = gather_images(local_out, unit_ids, total * ns, device, partial_sums=sums)  # the single exchange of the run
     psnr_mean, ssim_mean = float(sums[0] / sums[2]), float(sums[1] / sums[2])
+    lpips_line = lpips_print = ""
+    if lpips_state is not None:
+        lpips_mean = float(sums[3] / sums[2])
+        lpips_line, lpips_print = f"LPIPS: {lpips_mean:.4f}\n", f", LPIPS {lpips_mean:.4f}"
     name = lambda u: f"{u // ns:06d}_{o.seeds[u % ns]:06d}.png"
     import PIL.Image
     for sub in ("images", "cond_images", "forward_images"):
@@ -139,8 +155,8 @@ def main(argv=None):
                 PIL.Image.fromarray(load_image_u8(files[u // ns], S).permute(1, 2, 0).numpy(), "RGB").save(
                     os.path.join(o.outdir, "cond_images", name(u)))
         with open(os.path.join(o.outdir, "results.txt"), "w") as f:
-            f.write(f"PSNR: {psnr_mean:.4f}\nSSIM: {ssim_mean:.4f}\nimages: {total * ns}\n")
-        print(f"PSNR {psnr_mean:.3f} dB, SSIM {ssim_mean:.4f} over {total * ns} images -> {o.outdir}", flush=True)
+            f.write(f"PSNR: {psnr_mean:.4f}\nSSIM: {ssim_mean:.4f}\n{lpips_line}images: {total * ns}\n")
+        print(f"PSNR {psnr_mean:.3f} dB, SSIM {ssim_mean:.4f}{lpips_print} over {total * ns} images -> {o.outdir}", flush=True)
     for j, u in enumerate(unit_ids):  # forward (measurement) images are written by the owning rank
         if fwds[j].shape[-1] == S:
             PIL.Image.fromarray(fwds[j][0].permute(1, 2, 0).cpu().numpy(), "RGB").save(

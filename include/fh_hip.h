@@ -302,6 +302,8 @@ int fh_conv2d_nhwc(const float* in, const float* w, const float* bias, const flo
  * of the fused GroupNorm input (fh_conv2d_x6_norm_nhwc*: values beyond +-4094 saturate).
  * Per calling host thread. */
 int fh_unet_set_precision(int mode);
+/* the calling host thread's mode (0..4), so that a caller which needs one mode can put back what it found */
+int fh_unet_get_precision(void);
 /* max over out[0 .. FH_AMAX_SLOTS) = max |x[i]| (all 0 for n = 0): the magnitude the half-split convolution scales its
  * activation operand by.  FH_AMAX_SLOTS partial maxima instead of one value because same-address atomics serialise. */
 #define FH_AMAX_SLOTS 16
@@ -454,6 +456,28 @@ int fh_dense_rank2(const double* A, double* out, int bs, int64_t d, const double
 int64_t fh_metrics_scratch_doubles(int N, int C, int H, int W);
 int fh_metrics_u8(const uint8_t* a, const uint8_t* b, int N, int C, int H, int W, double* scratch, double* ssim_out,
                   double* psnr_out, void* stream);
+
+/* LPIPS v0.1 with the VGG16 backbone (generate_conditional.py:499-583: lpips.LPIPS(net='vgg') on (x / 255 - 0.5) * 2) - the
+ * streaming kernels around the thirteen 3 x 3 convolutions, which are fh_conv2d_x6_nhwc / fh_conv2d_nhwc.  Activations are
+ * float32 NHWC; both images of a pair travel in ONE batch of 2N: [0, N) = image a, [N, 2N) = image b.
+ *   fh_lpips_prep_u8:      a, b uint8 [N][3][H][W] -> out [2N][H][W][32], out[.., c] = table[c][v] for c < 3 (table: 3 x 256
+ *                          floats, the caller's ((v / 255 - 0.5) * 2 - shift_c) / scale_c rounded once from float64), 0 for
+ *                          c = 3..31 (the convolutions need Cin % 32 == 0).
+ *   fh_relu_f32:           x = max(x, 0) in place over n floats (n % 4 == 0, x 16-byte aligned).
+ *   fh_relu_maxpool2_nhwc: out [N][H/2][W/2][C] = max(0, max over the 2 x 2 window) of in [N][H][W][C]; C % 4 == 0; an odd last
+ *                          row / column is dropped (torch.nn.functional.max_pool2d(x, 2, 2)).
+ *   fh_lpips_tap:          feat [2N][H][W][C] is the RAW output of a tap's convolution (the ReLU is applied on read), lin [C]
+ *                          the tap's non-negative channel weights.  out[n * out_stride] = mean_{h,w} sum_c lin_c
+ *                          (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2 with |.| the channel 2-norm at the pixel, a = relu(feat[n]),
+ *                          b = relu(feat[N + n]).  Nothing normalised is written back.  float64 arithmetic and sums, block
+ *                          partials in a fixed order: deterministic, independent of n.  C in {64, 128, 256, 512} (else
+ *                          FH_ESIZE).  scratch: fh_lpips_tap_scratch_doubles(N) doubles. */
+int fh_lpips_prep_u8(const uint8_t* a, const uint8_t* b, const float* table, float* out, int N, int H, int W, void* stream);
+int fh_relu_f32(float* x, int64_t n, void* stream);
+int fh_relu_maxpool2_nhwc(const float* in, float* out, int N, int H, int W, int C, void* stream);
+int64_t fh_lpips_tap_scratch_doubles(int N);
+int fh_lpips_tap(const float* feat, const float* lin, int N, int H, int W, int C, double* scratch, double* out,
+                 int out_stride, void* stream);
 
 #ifdef __cplusplus
 }
