@@ -79,6 +79,7 @@ _SIGS = {
     "fh_read_scalars": ([C.c_void_p, c_dp, C.POINTER(C.c_double), C.c_int, C.c_void_p], C.c_int),
     "fh_conv_circ": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p], C.c_int),
+    "fh_channel_mix": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_amm": ([C.c_void_p, C.POINTER(FhProblem), c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_dense_matvec_scratch_doubles": ([C.c_int, C.c_int64], C.c_int64),
     "fh_dense_matvec": ([c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p], C.c_int),
@@ -241,6 +242,14 @@ class Context:
 
     def axpby(self, alpha, a, beta, b, out):
         check(self.lib.fh_axpby(float(alpha), ptr(a), float(beta), ptr(b), ptr(out), a.numel(), stream()), "fh_axpby")
+        return out
+
+    def channel_mix(self, x, out, w, adjoint=False):
+        """out[N,1,S,S] = sum_c w[c] x[N,3,S,S][:, c], or its adjoint out[N,3,S,S] = w[c] x[N,1,S,S]; float64, w on the device"""
+        nimg = x.numel() // ((1 if adjoint else 3) * self.S * self.S)
+        assert x.dtype == out.dtype == w.dtype == torch.float64 and w.numel() == 3
+        assert out.numel() == nimg * (3 if adjoint else 1) * self.S * self.S
+        check(self.lib.fh_channel_mix(self.h, ptr(x), ptr(out), ptr(w), nimg, int(adjoint), stream()), "fh_channel_mix")
         return out
 
     def conv(self, x, out, taps, planes, stride=1, adjoint=False):

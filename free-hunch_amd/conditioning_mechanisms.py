@@ -62,7 +62,11 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
     return 10 ** (frac * (math.log10(rtol_max) - math.log10(rtol_min)) + math.log10(rtol_min))
 
 
-_OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "super_resolution": 2}
+# fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
+_OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "super_resolution": 2, "colorization": 3, "noise": 0}
+_MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
+_BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
+                 "'colorization', or 'noise'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -85,10 +89,14 @@ def _problem(operator, cov, sigma_y2):
     p.m, p.ldm = m, cov.C.M_dev.shape[1]
     p.D, p.r, p.B, p.M = (cov.C.D.data_ptr(), cov.C.r.data_ptr(), cov.famC.B.data_ptr(), cov.C.M_dev.data_ptr())
     keep = [cov.C.D, cov.C.r, cov.famC.B, cov.C.M_dev]
-    if operator.name == "inpainting":
+    if operator.name in _MASKED:
         mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
         p.mask = mask.data_ptr()
         keep.append(mask)
+    elif operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
+        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
+        p.ntaps, p.tap_w = 3, w.data_ptr()
+        keep.append(w)
     else:
         t = operator.taps
         if t.sep is not None and operator.name != "super_resolution":
@@ -107,7 +115,8 @@ def _problem(operator, cov, sigma_y2):
 
 
 def _sigma_y2(operator):
-    """`sigma_s.clip(min=0.001)**2` evaluated in float32 like the reference (:386, :491), SR also clips at 1e-2 (:642)."""
+    """`sigma_s.clip(min=0.001)**2` evaluated in float32 like the reference (:386, :491), SR also clips at 1e-2 (:642);
+    colorization and denoising follow the blur / inpainting rule."""
     s = operator.sigma_s.detach().cpu().float().clip(min=0.001)
     if operator.name == "super_resolution":
         s = s.clip(min=1e-2)
@@ -124,16 +133,18 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     dev = cov.device
     name = operator.name
     if name not in _OP_CODE:
-        raise ValueError("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', "
-                         "'motion_blur', or 'inpainting'.")
+        raise ValueError(_BAD_OPERATOR)
     prob, keep = _problem(operator, cov, _sigma_y2(operator))
     prob.cg_scipy = int(bool(scipy_cg))
     y64 = y.detach().to(device=dev, dtype=F64).contiguous()
     x64 = x0_mean.detach().to(device=dev, dtype=F64).contiguous()
     # b = y - A x0_mean
-    if name == "inpainting":
+    if name in _MASKED:
         mask = keep[-1].view_as(x64)
         b = ctx.axpby(1.0, (mask * y64).contiguous(), -1.0, (mask * x64).contiguous(), torch.empty_like(x64))
+    elif name == "colorization":  # one measurement plane per image
+        ax = operator._mix(x64)
+        b = ctx.axpby(1.0, y64, -1.0, ax, ax)
     else:
         ax = operator._conv(x64, stride=prob.stride)
         b = ctx.axpby(1.0, y64, -1.0, ax, ax)
@@ -144,14 +155,16 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
         maxiter = 1000 if scipy_cg else 5000
     _lib.check(ctx.lib.fh_cg_solve(ctx.h, C.byref(prob), b.data_ptr(), sol.data_ptr(), rtol, 0.0, maxiter,
                                    C.byref(info), _lib.stream()), "fh_cg_solve")
-    if info.niter == (1000 if scipy_cg else (5000 if name == "inpainting" else 2000)):  # the reference's (inconsistent) guards
+    if info.niter == (1000 if scipy_cg else (5000 if name in _MASKED else 2000)):  # the reference's (inconsistent) guards
         warn("CG not converge.")
     if info_out is not None:
         info_out.append({"niter": info.niter, "optimal": bool(info.optimal), "residual_norm": info.residual_norm,
                          "rtol": rtol})
     solve_customcuda.last_solution = sol  # the measurement-space CG solution u (mat = A^T u); read by the parity tests
-    if name == "inpainting":
+    if name in _MASKED:
         return sol
+    if name == "colorization":
+        return operator._mix(sol, adjoint=True)
     return operator._conv(sol, stride=prob.stride, adjoint=True)
 
 
@@ -167,8 +180,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     op0, cov0 = operators[0], covariance_models[0]
     name = op0.name
     if name not in _OP_CODE:
-        raise ValueError("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', "
-                         "'motion_blur', or 'inpainting'.")
+        raise ValueError(_BAD_OPERATOR)
     dev, S = cov0.device, cov0.S
     # scratch sized for the whole batch; one context per lock-step GROUP (keyed by the group's first image slot), so
     # that equal-sized groups running concurrently from different host threads never share CG vectors or graph caches
@@ -185,7 +197,9 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             "lock-step images must share operator type and factor count"
         per.D[b], per.r[b], per.B[b], per.M[b] = (cov.C.D.data_ptr(), cov.C.r.data_ptr(), cov.famC.B.data_ptr(),
                                                   cov.C.M_dev.data_ptr())
-        if name == "inpainting":
+        if name == "colorization":
+            assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
+        if name in _MASKED:
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
             per.mask[b] = mk.data_ptr()
@@ -207,9 +221,17 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             ctx.conv(v, out, t, planes, prob.stride, adjoint)
         return out
 
-    if name == "inpainting":
+    def mix(v, adjoint):
+        """op0's channel mix on the whole batch"""
+        out = torch.empty(B, 3 if adjoint else 1, S, S, dtype=F64, device=dev)
+        return ctx.channel_mix(v, out, op0.weights, adjoint)
+
+    if name in _MASKED:
         mask = torch.cat([k.view(1, 3, S, S) for k in keep[-B:]], 0)
         b_vec = ctx.axpby(1.0, (mask * y64).contiguous(), -1.0, (mask * x64).contiguous(), torch.empty_like(x64))
+    elif name == "colorization":
+        ax = mix(x64, False)
+        b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
     else:
         ax = conv(x64, False)
         b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
@@ -220,19 +242,20 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     _lib.check(ctx.lib.fh_cg_solve_batched(ctx.h, C.byref(prob), C.byref(per), b_vec.data_ptr(), sol.data_ptr(), rtols,
                                            0.0, 5000, infos, _lib.stream()), "fh_cg_solve_batched")
     for b in range(B):
-        if infos[b].niter == (5000 if name == "inpainting" else 2000):
+        if infos[b].niter == (5000 if name in _MASKED else 2000):
             warn("CG not converge.")
         if infos_out is not None:
             infos_out.append({"niter": infos[b].niter, "optimal": bool(infos[b].optimal),
                               "residual_norm": infos[b].residual_norm, "rtol": rtol})
-    return sol if name == "inpainting" else conv(sol, True)
+    if name in _MASKED:
+        return sol
+    return mix(sol, True) if name == "colorization" else conv(sol, True)
 
 
 def choose_solver(operator_name, operator, y, x0_mean, theta0_var=None, covariance_model=None, method="customcuda",
                   max_rtol=1, ortho_tf=None, sigma_t=None, use_rtol_func=False, info_out=None):
     if operator_name not in _OP_CODE:
-        raise ValueError("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', "
-                         "'motion_blur', or 'inpainting'.")
+        raise ValueError(_BAD_OPERATOR)
     if method == "customcuda":
         return solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, info_out)
     # The reference's two scipy variants run `scipy.sparse.linalg.cg` on the CPU in float32 with tol = 1e-4 (or rtol_func_2

@@ -69,6 +69,7 @@ struct fh_context {
   int t_parity;       // which half the next apply accumulates into
   // CG work vectors (n <= planes_max*S*S)
   double *cg_r, *cg_p, *cg_ap, *w0, *w1, *w2;
+  double* deff;       // [nimg_max][S][S] colorization, no factor columns: D_eff = sum_c w_c^2 D_c per image (per solve; allocated by the first such solve)
   fh_cg_state* cg_state;
   fh_cg_state* h_state;  // pinned host mirror of cg_state (read back every few iterations)
   double* h_scal;        // pinned host staging for fh_read_scalars (64 doubles)

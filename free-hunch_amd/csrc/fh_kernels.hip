@@ -48,14 +48,16 @@ static inline PtrTab tab1(const double* q) {
 // ------------------------------------------------------------------------------------------------
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-template <bool BT, int TM, int TN = TM>  // TM x TN MFMA tiles (16x16) per wave: workgroup tile 32 TM x 32 TN
+// PPI: planes per image (3 colour planes; 1 for the one-plane measurement of the colorization operator) - only the
+// image a workgroup asks the `done` flag of depends on it
+template <bool BT, int TM, int TN = TM, int PPI = 3>  // TM x TN MFMA tiles (16x16) per wave: workgroup tile 32 TM x 32 TN
 __global__ __launch_bounds__(256) void k_gemm_f64(const double* __restrict__ A, const double* __restrict__ B,
                                                   double* __restrict__ C, int M, int N, int K, int lda, int ldb,
                                                   int ldc, int64_t sA, int64_t sB, int64_t sC,
                                                   const fh_cg_state* __restrict__ states, int rows_per_plane,
                                                   const double* __restrict__ add, double add_scale) {
   constexpr int BM = 32 * TM, BN = 32 * TN, BK = 32, LD = BK + 2;
-  IMG_GUARD(states, ((int)blockIdx.z + (int)(blockIdx.y * BM) / rows_per_plane) / 3);
+  IMG_GUARD(states, ((int)blockIdx.z + (int)(blockIdx.y * BM) / rows_per_plane) / PPI);
   __shared__ __align__(16) double As[2][BM][LD];
   __shared__ __align__(16) double Bs[2][BN][LD];
   A += sA * blockIdx.z;
@@ -193,14 +195,14 @@ struct fh_diag_tab {
   const double* D[FH_MAX_BATCH];  // null table (D[0] == nullptr): no scaling
 };
 
-template <bool INV>
+template <bool INV, int PPI = 3>  // PPI: planes per image (3, or 1 for the colorization operator's measurement plane)
 __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, const double* __restrict__ X,
                                                  double* __restrict__ C, int S, int planes,
                                                  const fh_cg_state* __restrict__ states, const double* __restrict__ add,
                                                  double add_scale, fh_diag_tab dg, double* __restrict__ dot_part,
                                                  int dot_stride) {
   // dot_part != null (with add): the workgroup also leaves sum(add .* out) of every (plane, tile) it completes in
-  // dot_part[image * dot_stride + (plane % 3) * tiles + tile] - the p.Ap reduction of the CG iteration rides in the pass
+  // dot_part[image * dot_stride + (plane % PPI) * tiles + tile] - the p.Ap reduction of the CG iteration rides in the pass
   // that produces Ap (A p = sigma_y^2 p + ..., add = p), summed later in a fixed order
   // K chunks of 64 (two per plane at S = 256): the per-chunk cost besides the 16 MFMA pairs - LDS stores, the barrier, the
   // wait for the prefetched rows - was ~65 % of a 32-wide chunk's time (measured 14.4 us per pass at BK = 32, 36 % of the f64
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
   // planes of this workgroup: p = blockIdx.z, + gridDim.z, ...  (finished images of a CG batch are skipped)
   int pl[8], npl = 0;
   for (int p = blockIdx.z; p < planes && npl < 8; p += gridDim.z)
-    if (states == nullptr || states[p / 3].done == 0) pl[npl++] = p;
+    if (states == nullptr || states[p / PPI].done == 0) pl[npl++] = p;
   const int total = npl * nkc;
   if (total == 0) return;
   double ra[NP8][8];
@@ -293,7 +295,7 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
       const int plane = pl[t / nkc];
       double* Cp = C + (int64_t)plane * S * S;
       const double* Ap = add != nullptr ? add + (int64_t)plane * S * S : nullptr;
-      const double* Dp = dg.D[0] != nullptr ? dg.D[plane / 3] + (int64_t)(plane % 3) * S * S : nullptr;
+      const double* Dp = dg.D[0] != nullptr ? dg.D[plane / PPI] + (int64_t)(plane % PPI) * S * S : nullptr;
       const int col = r0 + rw + li;
       double dsum = 0.0;
 #pragma unroll
@@ -321,7 +323,7 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
         __shared__ double dred[4];
         dsum = block_sum_256(dsum, dred);
         if (tid == 0)
-          dot_part[(int64_t)(plane / 3) * dot_stride + (plane % 3) * (int)(gridDim.x * gridDim.y) + blockIdx.y * gridDim.x +
+          dot_part[(int64_t)(plane / PPI) * dot_stride + (plane % PPI) * (int)(gridDim.x * gridDim.y) + blockIdx.y * gridDim.x +
                    blockIdx.x] = dsum;
       }
       acc_e = double4_t{0.0, 0.0, 0.0, 0.0};
@@ -368,15 +370,30 @@ __global__ __launch_bounds__(256) void k_dct_moments(const double* __restrict__ 
 // b_w = b_h = the DCT basis (or its transpose) gives the 2-D DCT-II / DCT-III; a separable blur folded into the bases
 // (fh_problem.fold_*) makes the same two passes compute dct2(A^T x) or A(idct2(x)).
 static int dct2d_launch_bases(fh_context* ctx, const double* in, double* out, int planes, const double* b_w, const double* b_h,
-                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st);
+                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st, int ppi = 3);
+
+// the two launches of a symmetric 2-D pass: along W into the context's intermediate, then along H with the epilogue operands
+template <bool INV, int PPI>
+static void dct_sym_pair(fh_context* ctx, dim3 grid, size_t lds, hipStream_t st, const double* sym_w, const double* sym_h,
+                         const double* in, double* out, int planes, const fh_cg_state* states, const double* add,
+                         double add_scale, const fh_diag_tab& dg, double* dot_part, int dot_stride) {
+  fh_diag_tab none;
+  memset(&none, 0, sizeof(none));
+  hipLaunchKernelGGL((k_dct_sym<INV, PPI>), grid, dim3(256), lds, st, sym_w, in, ctx->tmp_img, ctx->S, planes, states,
+                     (const double*)nullptr, 0.0, none, (double*)nullptr, 0);
+  hipLaunchKernelGGL((k_dct_sym<INV, PPI>), grid, dim3(256), lds, st, sym_h, (const double*)ctx->tmp_img, out, ctx->S, planes,
+                     states, add, add_scale, dg, dot_part, dot_stride);
+}
 
 // the two symmetric passes: tmp = (X P_w^T)^T, out = P_h X P_w^T (+ add_scale * add); sym_* = packed half bases [2][S/2][S/2]
 static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int planes, const double* sym_w,
                             const double* sym_h, int inverse, const double* add, double add_scale,
                             const fh_cg_state* states, hipStream_t st, const fh_batch* diag = nullptr,
-                            double* dot_part = nullptr, int dot_stride = 0, int* dot_nparts = nullptr) {
+                            double* dot_part = nullptr, int dot_stride = 0, int* dot_nparts = nullptr, int ppi = 3) {
+  // ppi: planes per image (3; 1 = the one-plane measurement of the colorization operator: `planes` images, diag->D[i] one plane)
   const int S = ctx->S, H = S / 2;
   if (planes > ctx->planes_max || S % 128 != 0) return FH_ESIZE;
+  if (ppi != 1 && ppi != 3) return FH_EINVAL;
   const int gx = S / 32, gy = H / 32;
   int gz = 256 / (gx * gy);
   if (gz < (planes + 7) / 8) gz = (planes + 7) / 8;
@@ -390,46 +407,58 @@ static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int 
                                  140 * 1024));
     FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  140 * 1024));
+    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<false, 1>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<true, 1>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
     attr_set = true;
   }
   const dim3 grid(gx, gy, gz);
-  fh_diag_tab none, dg;
-  memset(&none, 0, sizeof(none));
+  fh_diag_tab dg;
   memset(&dg, 0, sizeof(dg));
   if (diag != nullptr)
     for (int i = 0; i < diag->nimg && i < FH_MAX_BATCH; ++i) dg.D[i] = diag->D[i];
-  if (add == nullptr || 3 * gx * gy > 256) dot_part = nullptr;  // (the consumer sums <= 256 partials per image)
-  if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? 3 * gx * gy : 0;
-  if (inverse) {
-    hipLaunchKernelGGL(k_dct_sym<true>, grid, dim3(256), lds, st, sym_w, in, ctx->tmp_img, S, planes, states,
-                       (const double*)nullptr, 0.0, none, (double*)nullptr, 0);
-    hipLaunchKernelGGL(k_dct_sym<true>, grid, dim3(256), lds, st, sym_h, (const double*)ctx->tmp_img, out, S, planes, states,
-                       add, add_scale, dg, dot_part, dot_stride);
+  if (add == nullptr || ppi * gx * gy > 256) dot_part = nullptr;  // (the consumer sums <= 256 partials per image)
+  if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? ppi * gx * gy : 0;
+  if (ppi == 1) {  // one plane per image: the same two passes, image = plane
+    if (inverse) dct_sym_pair<true, 1>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
+    else dct_sym_pair<false, 1>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
   } else {
-    hipLaunchKernelGGL(k_dct_sym<false>, grid, dim3(256), lds, st, sym_w, in, ctx->tmp_img, S, planes, states,
-                       (const double*)nullptr, 0.0, none, (double*)nullptr, 0);
-    hipLaunchKernelGGL(k_dct_sym<false>, grid, dim3(256), lds, st, sym_h, (const double*)ctx->tmp_img, out, S, planes, states,
-                       add, add_scale, dg, dot_part, dot_stride);
+    if (inverse) dct_sym_pair<true, 3>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
+    else dct_sym_pair<false, 3>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
   }
   FH_LAUNCH_CHECK();
   return 0;
 }
 
 static int dct2d_launch(fh_context* ctx, const double* in, double* out, int planes, int inverse,
-                        const fh_cg_state* states, hipStream_t st) {
+                        const fh_cg_state* states, hipStream_t st, int ppi = 3, const double* add = nullptr,
+                        double add_scale = 0.0, double* dot_part = nullptr, int dot_stride = 0, int* dot_nparts = nullptr) {
   static const bool no_sym = getenv("FH_DCT_NOSYM") != nullptr;  // A/B switch: the dense passes
   if (ctx->sym_fwd != nullptr && !no_sym) {
     const double* sb = inverse ? ctx->sym_inv : ctx->sym_fwd;
-    return dct2d_launch_sym(ctx, in, out, planes, sb, sb, inverse, nullptr, 0.0, states, st);
+    return dct2d_launch_sym(ctx, in, out, planes, sb, sb, inverse, add, add_scale, states, st, nullptr, dot_part, dot_stride,
+                            dot_nparts, ppi);
   }
   const double* b1 = inverse ? ctx->basis_t : ctx->basis;
-  return dct2d_launch_bases(ctx, in, out, planes, b1, b1, nullptr, 0.0, states, st);
+  return dct2d_launch_bases(ctx, in, out, planes, b1, b1, add, add_scale, states, st, ppi);
 }
 
 static int dct2d_launch_bases(fh_context* ctx, const double* in, double* out, int planes, const double* b1, const double* b2,
-                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st) {
+                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st, int ppi) {
   const int S = ctx->S;
   if (planes > ctx->planes_max) return FH_ESIZE;
+  if (ppi == 1) {  // one plane per image (colorization): the 32 x 32 tiles (the smallest: a batch has few planes here; not tuned)
+    dim3 g1((S + 31) / 32, (planes * S + 31) / 32, 1);
+    hipLaunchKernelGGL((k_gemm_f64<true, 1, 1, 1>), g1, dim3(256), 0, st, in, b1, ctx->tmp_img, planes * S, S, S, S, S, S,
+                       (int64_t)0, (int64_t)0, (int64_t)0, states, S, (const double*)nullptr, 0.0);
+    dim3 g2((S + 31) / 32, (S + 31) / 32, planes);
+    hipLaunchKernelGGL((k_gemm_f64<false, 1, 1, 1>), g2, dim3(256), 0, st, b2, (const double*)ctx->tmp_img, out, S, S, S, S,
+                       S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states, 1 << 30, add, add_scale);
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
+  if (ppi != 3) return FH_EINVAL;
   // Tile choice by workgroup count (256 CUs, the GEMMs are MFMA-bound: what matters is an even number of tile-units per
   // CU).  64x64 tiles halve the LDS/global traffic per flop but S = 256, 24 planes gives 384 of them = 1.5 per CU
   // (half the CUs carry two: 24 us); 64x32 tiles give 768 = exactly 3 half-size units per CU.
@@ -1135,6 +1164,52 @@ __global__ __launch_bounds__(256) void k_mask(fh_batch per, const double* __rest
     if (add != nullptr) v = fma(add_scale, add[i], v);
     out[i] = v;
   }
+}
+
+// Channel mix of the colorization operator (grid z = image, one 16-byte pixel pair per thread, `pairs` = S*S/2 per plane):
+//   ADJ = 0:  out[img] = sum_c w[c] * in[img][c]  (+ add_scale * add[img])        in [nimg][3][S][S] -> out [nimg][S][S]
+//   ADJ = 1:  out[img][c] = w[c] * in[img]                                          in [nimg][S][S] -> out [nimg][3][S][S]
+// w: three device doubles, the same for every image.  The sum runs c = 0, 1, 2 in one fma chain.
+template <bool ADJ>
+__global__ __launch_bounds__(256) void k_channel_mix(const double* __restrict__ in, double* __restrict__ out,
+                                                     const double* __restrict__ w, int64_t pairs,
+                                                     const double* __restrict__ add, double add_scale,
+                                                     const fh_cg_state* __restrict__ states) {
+  const int img = blockIdx.z;
+  IMG_GUARD(states, img);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pairs) return;
+  const double w0 = w[0], w1 = w[1], w2 = w[2];
+  if (ADJ) {
+    const double2 v = reinterpret_cast<const double2*>(in + (int64_t)img * 2 * pairs)[i];
+    double2* o = reinterpret_cast<double2*>(out + (int64_t)img * 6 * pairs);
+    o[i] = make_double2(w0 * v.x, w0 * v.y);
+    o[pairs + i] = make_double2(w1 * v.x, w1 * v.y);
+    o[2 * pairs + i] = make_double2(w2 * v.x, w2 * v.y);
+  } else {
+    const double2* x = reinterpret_cast<const double2*>(in + (int64_t)img * 6 * pairs);
+    const double2 a = x[i], b = x[pairs + i], c = x[2 * pairs + i];
+    double2 v = make_double2(fma(w2, c.x, fma(w1, b.x, w0 * a.x)), fma(w2, c.y, fma(w1, b.y, w0 * a.y)));
+    if (add != nullptr) {
+      const double2 ad = reinterpret_cast<const double2*>(add + (int64_t)img * 2 * pairs)[i];
+      v = make_double2(fma(add_scale, ad.x, v.x), fma(add_scale, ad.y, v.y));
+    }
+    reinterpret_cast<double2*>(out + (int64_t)img * 2 * pairs)[i] = v;
+  }
+}
+
+// D_eff[img] = sum_c w[c]^2 D_c[img]: the diagonal of A C A^T in the DCT basis while the covariance has no factor columns
+// (the 2-D DCT acts per plane, so dct2 commutes with the channel mix: A C A^T u = idct2(D_eff .* dct2(u)))
+__global__ __launch_bounds__(256) void k_channel_deff(fh_batch per, const double* __restrict__ w, double* __restrict__ deff,
+                                                      int64_t pairs) {
+  const int img = blockIdx.z;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pairs) return;
+  const double w0 = w[0], w1 = w[1], w2 = w[2];
+  const double2* D = reinterpret_cast<const double2*>(per.D[img]);
+  const double2 a = D[i], b = D[pairs + i], c = D[2 * pairs + i];
+  reinterpret_cast<double2*>(deff + (int64_t)img * 2 * pairs)[i] =
+      make_double2(fma(w2 * w2, c.x, fma(w1 * w1, b.x, w0 * w0 * a.x)), fma(w2 * w2, c.y, fma(w1 * w1, b.y, w0 * w0 * a.y)));
 }
 
 constexpr int kDotBlocks = 256;
@@ -2011,6 +2086,32 @@ static int conv_launch(fh_context* ctx, const double* in, double* out, const int
 // ------------------------------------------------------------------------------------------------
 // dot_part / dot_nparts (CG only): where the operator's last pass can also reduce u . (A u) per image it writes *dot_nparts
 // block partials per image to dot_part (stride kCgScratch) - the caller then skips its own dot kernel; else *dot_nparts = 0
+// serialises hipGraph captures (cg_graph_for) against the legacy-stream work of context creation / destruction, see there
+static std::mutex g_capture_mu;
+
+// colorization with no factor columns on the symmetric DCT passes: A C A^T is diagonal in the DCT basis (D_eff)
+static bool colorize_deff_route(const fh_context* ctx, const fh_problem* p) {
+  static const bool no_sym = getenv("FH_DCT_NOSYM") != nullptr;
+  return p->op == 3 && p->use_dct && p->m == 0 && ctx->sym_fwd != nullptr && !no_sym;
+}
+
+// once per solve (and per fh_amm call): D_eff of every image into the context's scratch, before the first apply
+static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch& per, hipStream_t st) {
+  if (!colorize_deff_route(ctx, p)) return 0;
+  if (p->tap_w == nullptr || per.nimg < 1 || per.nimg > ctx->nimg_max) return FH_EINVAL;
+  for (int i = 0; i < per.nimg; ++i)
+    if (per.D[i] == nullptr) return FH_EINVAL;
+  if (ctx->deff == nullptr) {  // first colorization solve of this context (allocation under the capture lock, as context creation)
+    std::lock_guard<std::mutex> capture_lock(g_capture_mu);
+    FH_CHECK(hipMalloc(&ctx->deff, sizeof(double) * ctx->S * ctx->S * ctx->nimg_max));
+  }
+  const int64_t pairs = (int64_t)ctx->S * ctx->S / 2;
+  hipLaunchKernelGGL(k_channel_deff, dim3((unsigned)((pairs + 255) / 256), 1, (unsigned)per.nimg), dim3(256), 0, st, per,
+                     p->tap_w, ctx->deff, pairs);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
 static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* u, double* out,
                       const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr) {
   if (dot_nparts != nullptr) *dot_nparts = 0;
@@ -2021,8 +2122,49 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   const int nimg = per.nimg;
   const int planes = p->planes * nimg;
   if (d != (int64_t)p->planes * S * S || p->planes != 3 || nimg < 1 || nimg > ctx->nimg_max) return FH_EINVAL;
+  if (p->op < 0 || p->op > 3) return FH_EINVAL;
   int rc;
   double *w0 = ctx->w0, *w1 = ctx->w1;
+  if (p->op == 3) {
+    // colorization: u, out are ONE plane per image, A = channel mix with the three weights in tap_w.  The 2-D DCT acts per
+    // plane, so it commutes with the mix: A C A^T u = idct2( sum_c w_c (C_dct (w_c dct2(u)))_c ) - one forward and one
+    // inverse DCT over nimg planes instead of 3 nimg
+    if (p->ntaps != 3 || p->tap_w == nullptr || p->stride != 1 || (S & 1)) return FH_EINVAL;
+    if (3 * nimg > ctx->planes_max) return FH_ESIZE;  // the work vectors hold three planes per image
+    const int64_t pairs = (int64_t)S * S / 2;
+    const dim3 cgrid((unsigned)((pairs + 255) / 256), 1, (unsigned)nimg);
+    const double* cw = p->tap_w;
+    if (!p->use_dct) {  // identity basis: broadcast, apply, reduce (+ sigma_y^2 u)
+      hipLaunchKernelGGL(k_channel_mix<true>, cgrid, dim3(256), 0, st, u, w0, cw, pairs, (const double*)nullptr, 0.0, states);
+      rc = rep_apply_launch(ctx, per, p->ldm, w0, w1, d, p->m, states, st);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_channel_mix<false>, cgrid, dim3(256), 0, st, (const double*)w1, out, cw, pairs, u, p->sigma_y2,
+                         states);
+      FH_LAUNCH_CHECK();
+      return 0;
+    }
+    if (colorize_deff_route(ctx, p)) {
+      // no factor columns: D_eff = sum_c w_c^2 D_c (colorize_prepare, once per solve) rides in the forward pass's epilogue
+      fh_batch de;
+      memset(&de, 0, sizeof(de));
+      de.nimg = nimg;
+      for (int i = 0; i < nimg; ++i) de.D[i] = ctx->deff + (int64_t)i * S * S;
+      rc = dct2d_launch_sym(ctx, u, w0, nimg, ctx->sym_fwd, ctx->sym_fwd, 0, nullptr, 0.0, states, st, &de, nullptr, 0, nullptr,
+                            1);
+      if (rc) return rc;
+      return dct2d_launch_sym(ctx, w0, out, nimg, ctx->sym_inv, ctx->sym_inv, 1, u, p->sigma_y2, states, st, nullptr, dot_part,
+                              kCgScratch, dot_nparts, 1);
+    }
+    rc = dct2d_launch(ctx, u, w1, nimg, 0, states, st, 1);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_channel_mix<true>, cgrid, dim3(256), 0, st, (const double*)w1, w0, cw, pairs, (const double*)nullptr,
+                       0.0, states);
+    rc = rep_apply_launch(ctx, per, p->ldm, w0, w1, d, p->m, states, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_channel_mix<false>, cgrid, dim3(256), 0, st, (const double*)w1, w0, cw, pairs, (const double*)nullptr,
+                       0.0, states);
+    return dct2d_launch(ctx, w0, out, nimg, 1, states, st, 1, u, p->sigma_y2, dot_part, kCgScratch, dot_nparts);
+  }
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
   const bool sep = p->ntaps2 > 0;  // separable PSF: two 1-D passes (blur only, stride 1)
@@ -2266,9 +2408,6 @@ extern "C" {
 
 int fh_version(void) { return 100; }
 
-// serialises hipGraph captures (cg_graph_for) against the legacy-stream work of context creation / destruction, see there
-static std::mutex g_capture_mu;
-
 int fh_context_create(fh_context** out, int S, int planes_max, int m_cap) {
   if (out == nullptr || S < 2 || S > 256 || (S & 1) || planes_max < 1 || m_cap < 0 || m_cap > FH_MAX_COLS)
     return FH_EINVAL;
@@ -2349,7 +2488,7 @@ int fh_context_destroy(fh_context* c) {
   std::lock_guard<std::mutex> capture_lock(g_capture_mu);
   void* bufs[] = {c->basis, c->basis_t, c->tmp_img, c->partial, c->gpartial, c->coef, c->cg_r,
                   c->cg_p,  c->cg_ap,   c->w0,      c->w1,      c->w2,       c->cg_state, c->sync,
-                  c->sym_fwd, c->sym_inv};
+                  c->sym_fwd, c->sym_inv, c->deff};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (auto& g : c->graphs)
@@ -2795,9 +2934,30 @@ int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* 
                      (hipStream_t)stream);
 }
 
+int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double* w, int nimg, int adjoint, void* stream) {
+  if (!ctx || !in || !out || !w || nimg < 1 || (ctx->S & 1)) return FH_EINVAL;
+  if (((uintptr_t)in | (uintptr_t)out) & 15) return FH_EINVAL;  // 16-byte accesses
+  if (nimg > 65535) return FH_ESIZE;                            // the image is grid dimension z
+  const int64_t pairs = (int64_t)ctx->S * ctx->S / 2;
+  const dim3 grid((unsigned)((pairs + 255) / 256), 1, (unsigned)nimg);
+  if (adjoint)
+    hipLaunchKernelGGL(k_channel_mix<true>, grid, dim3(256), 0, (hipStream_t)stream, in, out, w, pairs, (const double*)nullptr,
+                       0.0, (const fh_cg_state*)nullptr);
+  else
+    hipLaunchKernelGGL(k_channel_mix<false>, grid, dim3(256), 0, (hipStream_t)stream, in, out, w, pairs, (const double*)nullptr,
+                       0.0, (const fh_cg_state*)nullptr);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
 int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, void* stream) {
   if (!ctx || !p || !u || !out) return FH_EINVAL;
-  return amm_launch(ctx, p, batch_of(p), u, out, nullptr, (hipStream_t)stream);
+  if (p->op < 0 || p->op > 3) return FH_EINVAL;
+  if (p->op == 3 && (((uintptr_t)u | (uintptr_t)out) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
+  const fh_batch per = batch_of(p);
+  const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
+  if (rc) return rc;
+  return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
 }
 
 // One chunk of CG iterations for all images of the batch, enqueued on `st` (eagerly, or while the stream is being
@@ -2890,8 +3050,10 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (nimg < 1 || nimg > ctx->nimg_max || nimg > FH_MAX_BATCH) return FH_ESIZE;
   hipStream_t st = (hipStream_t)stream;
   const int S = ctx->S;
+  if (p->op < 0 || p->op > 3 || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
+  if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const int So = S / (p->op == 2 ? p->stride : 1);
-  const int64_t n = (int64_t)p->planes * So * So;  // measurement dimension per image
+  const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;    // per image: [2]
@@ -2900,7 +3062,8 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   for (int i = 0; i < FH_MAX_BATCH; ++i) rt.v[i] = i < nimg ? rtol_host[i] : 1.0;
   for (int i = 0; i < nimg; ++i)
     if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
-  int rc = 0;
+  int rc = colorize_prepare(ctx, p, per, st);
+  if (rc) return rc;
   if (!p->cg_scipy) {
     rc = amm_launch(ctx, p, per, b, ap, nullptr, st);  // A x0 with x0 = b
     if (rc) return rc;

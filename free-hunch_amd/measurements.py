@@ -337,6 +337,87 @@ class InpaintingOperator(LinearOperator):  # measurements.py:204-246
         return MaskGenerator(**mask_opt)(img)
 
 
+def _channel_weights(channel_weights):
+    w = (1.0 / 3.0,) * 3 if channel_weights is None else channel_weights
+    try:
+        w = tuple(float(v) for v in w)
+    except (TypeError, ValueError):
+        raise ValueError(f"channel_weights must be three finite numbers, got {channel_weights!r}") from None
+    if len(w) != 3 or not all(np.isfinite(v) for v in w):
+        raise ValueError(f"channel_weights must be three finite numbers, got {channel_weights!r}")
+    return w
+
+
+@register_operator(name="colorization")
+class ColorizationOperator(LinearOperator):  # measurements.py:74-84 (A = mean over the colour channels)
+    """y = sum_c w_c x_c + noise, one measurement plane per image.  `channel_weights` defaults to (1/3, 1/3, 1/3), the
+    reference's `mean(dim=1)`; the weights are shared by every image of a lock-step batch.  Forward and adjoint run in
+    float64 through fh_channel_mix."""
+
+    def __init__(self, in_shape, sigma_s, device, channel_weights=None, **kwargs):
+        self.device = torch.device(device)
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
+        self.out_shape = (1, 1, in_shape[-2], in_shape[-1])
+        self.channel_weights = _channel_weights(channel_weights)
+        self._w = None  # the three weights on the device, created on first use
+
+    @property
+    def weights(self):
+        if self._w is None:
+            self._w = torch.tensor(self.channel_weights, dtype=F64, device=self.device)
+        return self._w
+
+    def _mix(self, x, adjoint=False):
+        """float64 channel mix of an NCHW tensor ([N,3,S,S] -> [N,1,S,S], or its adjoint); returns float64."""
+        S = self.in_shape[-1]
+        x64 = x.detach().to(device=self.device, dtype=F64).reshape(-1, 1 if adjoint else 3, S, S).contiguous()
+        out = torch.empty(x64.shape[0], 3 if adjoint else 1, S, S, dtype=F64, device=self.device)
+        return self._ctx().channel_mix(x64, out, self.weights, adjoint)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        y = self._noise(self._mix(data).to(data.dtype), noiseless)
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        return self._mix(y, adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`, for DPS"""
+        return self._mix(v, adjoint=True).to(v.dtype)
+
+
+@register_operator(name="noise")
+class DenoiseOperator(LinearOperator):  # measurements.py:56-72 (A = I)
+    """y = x + sigma_s * randn.  Deviation from the reference: its class takes no `noiseless` argument and adds no noise
+    at all, so its own sampler (which calls `forward(x, noiseless=...)`) cannot run it; here `forward` has the signature
+    of the other operators and adds the measurement noise.  The solvers treat it as inpainting with an all-ones mask."""
+
+    def __init__(self, in_shape, sigma_s, device, **kwargs):
+        self.device = torch.device(device)
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
+        self.out_shape = tuple(in_shape)
+        self.mask = torch.ones(1, *in_shape[-3:], device=self.device)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        y = self._noise(data.clone(), noiseless)
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, data, flatten=False):
+        y = data.clone()
+        if flatten:
+            return y.reshape(y.shape[0], *self.in_shape[-3:])
+        return y
+
+    def forward_adjoint(self, v):
+        return v
+
+
 class MaskGenerator:  # measurements.py:248-318 (random / box / extreme; global numpy RNG, as the reference)
     def __init__(self, mask_type, mask_len_range=None, mask_prob_range=None, image_size=256, margin=(16, 16)):
         assert mask_type in ["box", "random", "both", "extreme"]

@@ -158,7 +158,9 @@ def main(argv=None):
             f.write(f"PSNR: {psnr_mean:.4f}\nSSIM: {ssim_mean:.4f}\n{lpips_line}images: {total * ns}\n")
         print(f"PSNR {psnr_mean:.3f} dB, SSIM {ssim_mean:.4f}{lpips_print} over {total * ns} images -> {o.outdir}", flush=True)
     for j, u in enumerate(unit_ids):  # forward (measurement) images are written by the owning rank
-        if fwds[j].shape[-1] == S:
+        if fwds[j].shape[-1] == S and fwds[j].shape[1] == 1:  # a one-channel measurement (colorization): 8-bit grayscale
+            PIL.Image.fromarray(fwds[j][0, 0].cpu().numpy(), "L").save(os.path.join(o.outdir, "forward_images", name(u)))
+        elif fwds[j].shape[-1] == S:
             PIL.Image.fromarray(fwds[j][0].permute(1, 2, 0).cpu().numpy(), "RGB").save(
                 os.path.join(o.outdir, "forward_images", name(u)))
     if world > 1:

@@ -183,9 +183,22 @@ int fh_read_scalars(fh_context* ctx, const double* scal, double* out_host, int k
 int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
                  const double* w, int ntaps, int halo, int planes, int stride, int adjoint, void* stream);
 
+/* Channel mix of the colorization operator, measurement_utils/measurements.py:74-84 (A = mean over the colour channels,
+ * here with three weights w[0..2] on the device; (1/3, 1/3, 1/3) is the reference's operator):
+ *   adjoint = 0:  in [nimg][3][S][S] -> out [nimg][S][S],     out = sum_c w[c] * in_c
+ *   adjoint = 1:  in [nimg][S][S]    -> out [nimg][3][S][S],  out_c = w[c] * in
+ * S is the context's image side; in, out 16-byte aligned (else FH_EINVAL), in != out. */
+int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double* w, int nimg, int adjoint, void* stream);
+
 /* the linear solve of conditioning_mechanisms.py:384-419 / 489-527 / 641-675 ------------------------ */
 typedef struct fh_problem {
-  int32_t op;            /* 0 inpainting, 1 blur (gaussian/motion), 2 super-resolution */
+  /* 0 inpainting (and denoising, A = I: an all-ones mask), 1 blur (gaussian/motion), 2 super-resolution, 3 colorization:
+   * A = the channel mix of fh_channel_mix with the three weights in tap_w (ntaps = 3; tap_dy / tap_dx unused), planes = 3 and
+   * d = 3 S S as for the others, but the measurement - u, b, x of fh_amm / fh_cg_solve[_batched] - is ONE plane per image,
+   * n = S S.  The 2-D DCT acts per plane, so with use_dct = 1  A C A^T u = idct2(sum_c w_c (C_dct (w_c dct2(u)))_c): one
+   * forward and one inverse DCT over one plane per image, and with m = 0 it is idct2(D_eff .* dct2(u)), D_eff = sum_c w_c^2 D_c.
+   * Any other value: FH_EINVAL. */
+  int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
   int32_t planes;        /* 3 * batch(=1) */
   int32_t stride;        /* SR scale factor, else 1 */
