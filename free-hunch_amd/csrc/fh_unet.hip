@@ -1626,32 +1626,128 @@ inline unsigned grid_for(int64_t work_items, int per_block = 256, int cap = 4096
   return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
+// Precision of the bf16-MFMA convolution kernels: 3 = exact 3-way split (fp32 accuracy, default), 1 = plain bf16 compute
+// (operands rounded to bf16, one product, fp32 accumulation) - the reduced-precision UNet mode, the counterpart of the
+// reference's use_fp16 torso (training/openai_fp16_util.py:15-32).  Process-wide: set before a forward / VJP.
+// Mode 4 (half-split, 32): two half-precision planes per operand, three products on the f16 MFMA (see split_scale above):
+// the host picks it per launch, so the switch is per host thread (the lock-step groups of a process launch concurrently).
+thread_local int g_conv_np = 3;
+
+// The launch of one split-bf16 convolution, a pure function of the layer: which kernel, which tile, which grid.  The
+// launcher, fh_conv2d_x6_gn_chunks (the size of the group-sum partials buffer, which fh_groupnorm_finalize reads back) and
+// fh_conv2d_x6_norm_supported are all derived from it.
+struct X6Plan {
+  bool reuse;  // k_conv_x6r (3 x 3 / stride 1 / pad 1, rows staged once for the three kernel rows) or the generic k_conv_x6
+  int bm, bn;  // output tile: pixels x channels (k_conv_x6r: bn = 128; k_conv_x6: 128 x 128, 64 x 128 or 64 x 64)
+  int segw;    // k_conv_x6r: pixels per row segment of the tile
+  int gl;      // k_conv_x6r: 1 = weight tile by LDS-DMA (the 256-pixel tile), 0 = staged through registers
+  dim3 grid, block;
+  bool norm;   // k_conv_x6r: GroupNorm(+SiLU) applied while the input tile is staged (fh_conv2d_x6_norm_nhwc)
+  int gn_bm;   // tile height the group-sum epilogue sees, 0 where the epilogue does not apply
+};
+
+X6Plan x6_plan(int ksplit, int N, int H, int W, int /*Cin: no tile depends on it*/, int Cout, int KH, int KW, int pad,
+               int stride, bool norm) {
+  // `norm` only picks the NORM template flag of the planned kernel: the tile is that of the plain launch, and a layer
+  // whose plan is not a row-reuse one has no fused form
+  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+  const int64_t M = (int64_t)N * Ho * Wo;
+  const int nb128 = (Cout + 127) / 128;
+  const int64_t b128 = ((M + 127) / 128) * nb128;
+  X6Plan p{};
+  p.bn = 128, p.norm = norm;
+  if (ksplit == 1 && Cout > 64 && b128 >= 384) {
+    // 128 x 128 tiles run as 8 waves (2 x 4, wave tile 64 x 32: 102 VGPRs, 4 waves per SIMD over two workgroups per CU);
+    // 256-pixel tiles (16 waves) once they still give every CU a workgroup
+    const bool r3 = KH == 3 && KW == 3 && pad == 1 && stride == 1 && M % 128 == 0;
+    const bool big = r3 && M % 256 == 0 && (M / 256) * nb128 >= 256;
+    p.reuse = true;
+    if (big && W % 256 == 0)
+      p.bm = 256, p.segw = 256;
+    else if (big && W == 128 && H % 2 == 0)
+      p.bm = 256, p.segw = 128;
+    else if (big && W == 64 && H % 4 == 0)
+      p.bm = 256, p.segw = 64;
+    else if (r3 && W % 128 == 0)
+      p.bm = 128, p.segw = 128;
+    else if (r3 && W == 64 && H % 2 == 0)
+      p.bm = 128, p.segw = 64;
+    else if (r3 && W == 32 && H % 4 == 0)
+      p.bm = 128, p.segw = 32;
+    else
+      p.reuse = false, p.bm = 128;
+    p.gl = p.bm == 256;
+  } else if (ksplit > 1 && Cout > 64 && b128 * ksplit >= 256) {
+    // small grids: 128 x 128 tiles (21 flop per byte pulled from L2 instead of 12.8) once split-K still fills the chip
+    p.bm = 128;
+  } else if (ksplit == 1 && Cout > 64 && ((M + 63) / 64) * nb128 >= 256) {
+    p.bm = 64;
+  } else {
+    p.bm = 64, p.bn = 64;
+  }
+  p.grid = dim3((unsigned)((M + p.bm - 1) / p.bm), (unsigned)((Cout + p.bn - 1) / p.bn), (unsigned)ksplit);
+  p.block = dim3(p.reuse ? 4 * p.bm : (p.bm == 128 ? 512 : 256));
+  // group sums: no split-K, 128-column tiles (so Cout > 64), no output tile that straddles two images, whole groups
+  p.gn_bm = (ksplit == 1 && Cout > 64 && p.bn == 128 && Cout % 32 == 0 && (Ho * Wo) % p.bm == 0) ? p.bm : 0;
+  return p;
+}
+
+// the five precision instantiations of one tile (fh_unet_set_precision)
+template <int SEGW, bool NORM, int BM, int GL>
+void launch_x6r(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  switch (g_conv_np) {
+    case 1: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL>), p.grid, p.block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL>), p.grid, p.block, 0, st, a); break;
+    case 16: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL, true>), p.grid, p.block, 0, st, a); break;
+    // half-split with LDS-DMA weights: three-slot weight ring + double-buffered activations (GL = 2)
+    case 32: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL == 1 ? 2 : GL, true>), p.grid, p.block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 3, GL>), p.grid, p.block, 0, st, a); break;
+  }
+}
+
+template <int MI, int NI, int WM, int WN, int MINW>
+void launch_x6(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  switch (g_conv_np) {
+    case 1: hipLaunchKernelGGL((k_conv_x6<MI, NI, WM, WN, MINW, 1>), p.grid, p.block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_conv_x6<MI, NI, WM, WN, MINW, 2>), p.grid, p.block, 0, st, a); break;
+    case 16: hipLaunchKernelGGL((k_conv_x6<MI, NI, WM, WN, MINW, 1, true>), p.grid, p.block, 0, st, a); break;
+    case 32: hipLaunchKernelGGL((k_conv_x6<MI, NI, WM, WN, MINW, 2, true>), p.grid, p.block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_conv_x6<MI, NI, WM, WN, MINW, 3>), p.grid, p.block, 0, st, a); break;
+  }
+}
+
+constexpr int tile_key(int bm, int w, int gl = 0) { return (bm * 1024 + w) * 2 + gl; }
+
+// one switch over the row-reuse combinations (BM, SEGW, GL); false for a plan no kernel is built for
+template <bool NORM>
+bool launch_x6r_tile(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  switch (tile_key(p.bm, p.segw, p.gl)) {
+    case tile_key(256, 256, 1): launch_x6r<256, NORM, 256, 1>(p, st, a); return true;
+    case tile_key(256, 128, 1): launch_x6r<128, NORM, 256, 1>(p, st, a); return true;
+    case tile_key(256, 64, 1): launch_x6r<64, NORM, 256, 1>(p, st, a); return true;
+    case tile_key(128, 128, 0): launch_x6r<128, NORM, 128, 0>(p, st, a); return true;
+    case tile_key(128, 64, 0): launch_x6r<64, NORM, 128, 0>(p, st, a); return true;
+    case tile_key(128, 32, 0): launch_x6r<32, NORM, 128, 0>(p, st, a); return true;
+  }
+  return false;
+}
+
+// the three generic tiles (BM, BN)
+bool launch_x6_tile(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  switch (tile_key(p.bm, p.bn)) {
+    case tile_key(128, 128): launch_x6<2, 1, 2, 4, 4>(p, st, a); return true;
+    case tile_key(64, 128): launch_x6<1, 2, 2, 2, 2>(p, st, a); return true;
+    case tile_key(64, 64): launch_x6<1, 1, 2, 2, 2>(p, st, a); return true;
+  }
+  return false;
+}
+
 }  // namespace
 
 // ================================================================================================
 // C ABI
 // ================================================================================================
 extern "C" {
-
-// Precision of the bf16-MFMA convolution kernels: 3 = exact 3-way split (fp32 accuracy, default), 1 = plain bf16 compute
-// (operands rounded to bf16, one product, fp32 accumulation) - the reduced-precision UNet mode, the counterpart of the
-// reference's use_fp16 torso (training/openai_fp16_util.py:15-32).  Process-wide: set before a forward / VJP.
-// Mode 4 (half-split, 32): two half-precision planes per operand, three products on the f16 MFMA (see split_scale above):
-// the host picks it per launch, so the switch is per host thread (the lock-step groups of a process launch concurrently).
-static thread_local int g_conv_np = 3;
-#define X6_DISPATCH(K1, K2, K3, K16, K32, ...)        \
-  do {                                               \
-    if (g_conv_np == 1)                              \
-      hipLaunchKernelGGL(K1, __VA_ARGS__);           \
-    else if (g_conv_np == 2)                         \
-      hipLaunchKernelGGL(K2, __VA_ARGS__);           \
-    else if (g_conv_np == 16)                        \
-      hipLaunchKernelGGL(K16, __VA_ARGS__);          \
-    else if (g_conv_np == 32)                        \
-      hipLaunchKernelGGL(K32, __VA_ARGS__);          \
-    else                                             \
-      hipLaunchKernelGGL(K3, __VA_ARGS__);           \
-  } while (0)
 
 int fh_unet_set_precision(int mode) {
   if (mode < 0 || mode > 4) return FH_EINVAL;
@@ -1683,8 +1779,8 @@ int fh_conv2d_splitk(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
   const int64_t blocks = ((M + 63) / 64) * ((Cout + 63) / 64);
   const int nchunks = KH * KW * (Cin / kBK);
   int z = 1;
-  static const int target = getenv("FH_SPLITK_TARGET") ? atoi(getenv("FH_SPLITK_TARGET")) : 2048;  // 64 x 64-tile blocks x z wanted (measured: 1024 -> 2048 +9 % on the 16^2 / 32^2 grids, 4096 no better)
-  static const int zmax = getenv("FH_SPLITK_MAX") ? atoi(getenv("FH_SPLITK_MAX")) : 8;
+  constexpr int target = 2048;  // 64 x 64-tile blocks x z wanted (measured: 1024 -> 2048 +9 % on the 16^2 / 32^2 grids, 4096 no better)
+  constexpr int zmax = 8;
   while (blocks * z < target && z < zmax && nchunks / (2 * z) >= 6) z *= 2;
   return z;
 }
@@ -1722,46 +1818,11 @@ int fh_conv2d_nhwc(const float* in, const float* w, const float* bias, const flo
   return 0;
 }
 
-// tile height (pixels) of the launch fh_conv2d_x6_nhwc takes for this layer, 0 when the group-sum epilogue does not apply
-// (split-K, the 64-column tile, output tiles that straddle two images, channels not a multiple of 32)
-static int x6_gn_tile(int ksplit, int64_t M, int HoWo, int Ho, int Wo, int Cout, int KH, int KW, int pad, int stride) {
-  if (ksplit != 1 || Cout <= 64 || Cout % 32 != 0) return 0;
-  const int64_t b128 = ((M + 127) / 128) * ((Cout + 127) / 128);
-  int bm = 0;
-  if (b128 >= 384) {
-    const bool r3 = !getenv("FH_X6_NOREUSE") && KH == 3 && KW == 3 && pad == 1 && stride == 1 && M % 128 == 0;
-    const bool big = r3 && !getenv("FH_X6_NOBIG") && M % 256 == 0 && (M / 256) * ((Cout + 127) / 128) >= 256;
-    if (big && (Wo % 256 == 0 || (Wo == 128 && Ho % 2 == 0) || (Wo == 64 && Ho % 4 == 0)))
-      bm = 256;
-    else
-      bm = 128;
-  } else if (((M + 63) / 64) * ((Cout + 127) / 128) >= 256) {
-    bm = 64;
-  }
-  return (bm > 0 && HoWo % bm == 0) ? bm : 0;
-}
-
-static int conv2d_x6_impl(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
-                          int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
-                          const fh_gn_epilogue* epi, void* stream);
-
-int fh_conv2d_x6_nhwc(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
-                      int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
-                      void* stream) {
-  return conv2d_x6_impl(in, wx, bias, res, out, ws, ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride, nullptr, stream);
-}
-
-int fh_conv2d_x6_nhwc_gn(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
-                         int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
-                         const fh_gn_epilogue* epi, void* stream) {
-  return conv2d_x6_impl(in, wx, bias, res, out, ws, ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride, epi, stream);
-}
-
 int fh_conv2d_x6_gn_chunks(int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride) {
   if (N < 1 || H < 1 || W < 1 || Cout < 1 || stride < 1) return 0;
+  const X6Plan p = x6_plan(ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride, false);
   const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  const int bm = x6_gn_tile(ksplit, (int64_t)N * Ho * Wo, Ho * Wo, Ho, Wo, Cout, KH, KW, pad, stride);
-  return bm ? (Ho * Wo / bm) * ((Cout + 127) / 128) : 0;
+  return p.gn_bm ? (Ho * Wo / p.gn_bm) * ((Cout + 127) / 128) : 0;
 }
 
 static int set_gn(ConvArgsX& a, const fh_gn_epilogue* epi, int chunks) {
@@ -1776,71 +1837,53 @@ static int set_gn(ConvArgsX& a, const fh_gn_epilogue* epi, int chunks) {
   return 0;
 }
 
-static int conv2d_x6_impl(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
-                          int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
-                          const fh_gn_epilogue* epi, void* stream) {
+// The one launch path of the split-bf16 convolution.  `norm`: the input is GroupNorm(+SiLU)'d through `ab_table` while the
+// tile is staged (3 x 3 / stride 1 / pad 1 layers whose plan is a row-reuse one, fh_conv2d_x6_norm_supported).
+static int conv2d_x6_launch(const float* in, bool norm, const float* ab_table, int act, const void* wx, const float* bias,
+                            const float* res, float* out, float* ws, int ksplit, int N, int H, int W, int Cin, int Cout,
+                            int KH, int KW, int pad, int stride, const fh_gn_epilogue* epi, void* stream) {
   if (!in || !wx || !out || N < 1 || H < 1 || W < 1 || Cin < kBK || Cin % kBK != 0 || Cout < 1 || stride < 1)
     return FH_EINVAL;
   if (ksplit < 1 || ksplit > 32 || (ksplit > 1 && !ws)) return FH_EINVAL;
+  const X6Plan p = x6_plan(ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride, norm);
+  if (norm && (!ab_table || !p.reuse)) return FH_EINVAL;
   ConvArgsX a;
-  a.ab = nullptr, a.act = 0;
-  {
-    const int rc = set_gn(a, epi, fh_conv2d_x6_gn_chunks(ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride));
-    if (rc) return rc;
-  }
+  a.ab = norm ? ab_table : nullptr, a.act = norm ? act : 0;
   a.in = in, a.wx = (const __bf16*)wx, a.bias = bias, a.res = res, a.out = out;
   a.N = N, a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout, a.KH = KH, a.KW = KW, a.pad = pad, a.stride = stride;
   a.Ho = (H + 2 * pad - KH) / stride + 1;
   a.Wo = (W + 2 * pad - KW) / stride + 1;
   a.ksplit = ksplit, a.ws = ws;
-  const int64_t M = (int64_t)N * a.Ho * a.Wo;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned Z = (unsigned)ksplit;
-  // 128 x 128 tiles run as 8 waves (2 x 4, wave tile 64 x 32: 102 VGPRs, 4 waves per SIMD over two workgroups per CU)
-  const int64_t b128 = ((M + 127) / 128) * ((Cout + 127) / 128);
-  if (ksplit == 1 && Cout > 64 && b128 >= 384) {
-    static const int no_reuse = getenv("FH_X6_NOREUSE") != nullptr;
-    const bool r3 = !no_reuse && KH == 3 && KW == 3 && pad == 1 && stride == 1 && M % 128 == 0;
-    static const int no_big = getenv("FH_X6_NOBIG") != nullptr;
-    const bool big = r3 && !no_big && M % 256 == 0 && (M / 256) * ((Cout + 127) / 128) >= 256;
-    const dim3 gbig((unsigned)(M / 256), (Cout + 127) / 128, 1);
-    static const int glds = getenv("FH_X6_GLDS") ? atoi(getenv("FH_X6_GLDS")) : 1;  // weight tile by LDS-DMA (default; 0 = register staging, the A/B switch)
-    static const int deep = getenv("FH_X6_DEEP") ? atoi(getenv("FH_X6_DEEP")) : 1;  // half-split mode: three-slot weight ring + double-buffered activations (0 = the two-slot pipeline, the A/B switch)
-    if (big && glds && W % 256 == 0)
-      X6_DISPATCH((k_conv_x6r<256, false, 256, 1, true>), (k_conv_x6r<256, false, 256, 2, true>), (k_conv_x6r<256, false, 256, 3, true>), (k_conv_x6r<256, false, 256, 1, true, true>), (deep ? k_conv_x6r<256, false, 256, 2, 2, true> : k_conv_x6r<256, false, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-    else if (big && glds && W == 128 && H % 2 == 0)
-      X6_DISPATCH((k_conv_x6r<128, false, 256, 1, true>), (k_conv_x6r<128, false, 256, 2, true>), (k_conv_x6r<128, false, 256, 3, true>), (k_conv_x6r<128, false, 256, 1, true, true>), (deep ? k_conv_x6r<128, false, 256, 2, 2, true> : k_conv_x6r<128, false, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-    else if (big && glds && W == 64 && H % 4 == 0)
-      X6_DISPATCH((k_conv_x6r<64, false, 256, 1, true>), (k_conv_x6r<64, false, 256, 2, true>), (k_conv_x6r<64, false, 256, 3, true>), (k_conv_x6r<64, false, 256, 1, true, true>), (deep ? k_conv_x6r<64, false, 256, 2, 2, true> : k_conv_x6r<64, false, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-    else if (big && W % 256 == 0)
-      X6_DISPATCH((k_conv_x6r<256, false, 256, 1>), (k_conv_x6r<256, false, 256, 2>), (k_conv_x6r<256, false, 256, 3>), (k_conv_x6r<256, false, 256, 1, false, true>), (k_conv_x6r<256, false, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-    else if (big && W == 128 && H % 2 == 0)
-      X6_DISPATCH((k_conv_x6r<128, false, 256, 1>), (k_conv_x6r<128, false, 256, 2>), (k_conv_x6r<128, false, 256, 3>), (k_conv_x6r<128, false, 256, 1, false, true>), (k_conv_x6r<128, false, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-    else if (big && W == 64 && H % 4 == 0)
-      X6_DISPATCH((k_conv_x6r<64, false, 256, 1>), (k_conv_x6r<64, false, 256, 2>), (k_conv_x6r<64, false, 256, 3>), (k_conv_x6r<64, false, 256, 1, false, true>), (k_conv_x6r<64, false, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-    else if (r3 && W % 128 == 0)
-      X6_DISPATCH((k_conv_x6r<128, false, 128, 1>), (k_conv_x6r<128, false, 128, 2>), (k_conv_x6r<128, false, 128, 3>), (k_conv_x6r<128, false, 128, 1, false, true>), (k_conv_x6r<128, false, 128, 2, false, true>), dim3((unsigned)(M / 128), (Cout + 127) / 128, 1), dim3(512), 0, st, a);
-    else if (r3 && W == 64 && H % 2 == 0)
-      X6_DISPATCH((k_conv_x6r<64, false, 128, 1>), (k_conv_x6r<64, false, 128, 2>), (k_conv_x6r<64, false, 128, 3>), (k_conv_x6r<64, false, 128, 1, false, true>), (k_conv_x6r<64, false, 128, 2, false, true>), dim3((unsigned)(M / 128), (Cout + 127) / 128, 1), dim3(512), 0, st, a);
-    else if (r3 && W == 32 && H % 4 == 0)
-      X6_DISPATCH((k_conv_x6r<32, false, 128, 1>), (k_conv_x6r<32, false, 128, 2>), (k_conv_x6r<32, false, 128, 3>), (k_conv_x6r<32, false, 128, 1, false, true>), (k_conv_x6r<32, false, 128, 2, false, true>), dim3((unsigned)(M / 128), (Cout + 127) / 128, 1), dim3(512), 0, st, a);
-    else
-      X6_DISPATCH((k_conv_x6<2, 1, 2, 4, 4, 1>), (k_conv_x6<2, 1, 2, 4, 4, 2>), (k_conv_x6<2, 1, 2, 4, 4, 3>), (k_conv_x6<2, 1, 2, 4, 4, 1, true>), (k_conv_x6<2, 1, 2, 4, 4, 2, true>), dim3((unsigned)((M + 127) / 128), (Cout + 127) / 128, 1), dim3(512), 0, st, a);
-  } else if (ksplit > 1 && Cout > 64 && b128 * ksplit >= 256 && !getenv("FH_X6_NOBIGSPLIT")) {
-    // small grids: 128 x 128 tiles (21 flop per byte pulled from L2 instead of 12.8) once split-K still fills the chip
-    X6_DISPATCH((k_conv_x6<2, 1, 2, 4, 4, 1>), (k_conv_x6<2, 1, 2, 4, 4, 2>), (k_conv_x6<2, 1, 2, 4, 4, 3>), (k_conv_x6<2, 1, 2, 4, 4, 1, true>), (k_conv_x6<2, 1, 2, 4, 4, 2, true>), dim3((unsigned)((M + 127) / 128), (Cout + 127) / 128, Z), dim3(512), 0, st, a);
-  } else if (ksplit == 1 && Cout > 64 && ((M + 63) / 64) * ((Cout + 127) / 128) >= 256) {
-    X6_DISPATCH((k_conv_x6<1, 2, 2, 2, 2, 1>), (k_conv_x6<1, 2, 2, 2, 2, 2>), (k_conv_x6<1, 2, 2, 2, 2, 3>), (k_conv_x6<1, 2, 2, 2, 2, 1, true>), (k_conv_x6<1, 2, 2, 2, 2, 2, true>), dim3((unsigned)((M + 63) / 64), (Cout + 127) / 128, 1), dim3(256), 0, st, a);
-  } else {
-    X6_DISPATCH((k_conv_x6<1, 1, 2, 2, 2, 1>), (k_conv_x6<1, 1, 2, 2, 2, 2>), (k_conv_x6<1, 1, 2, 2, 2, 3>), (k_conv_x6<1, 1, 2, 2, 2, 1, true>), (k_conv_x6<1, 1, 2, 2, 2, 2, true>), dim3((unsigned)((M + 63) / 64), (Cout + 63) / 64, Z), dim3(256), 0, st, a);
+  {
+    const int rc = set_gn(a, epi, p.gn_bm ? (a.Ho * a.Wo / p.gn_bm) * ((Cout + 127) / 128) : 0);
+    if (rc) return rc;
   }
+  hipStream_t st = (hipStream_t)stream;
+  const bool built = !p.reuse ? launch_x6_tile(p, st, a)
+                     : p.norm ? launch_x6r_tile<true>(p, st, a)
+                              : launch_x6r_tile<false>(p, st, a);
+  if (!built) return FH_ESIZE;
   if (ksplit > 1) {
-    const int64_t total = M * Cout;
+    const int64_t total = (int64_t)N * a.Ho * a.Wo * Cout;
     hipLaunchKernelGGL(k_splitk_reduce, dim3(grid_for(total)), dim3(256), 0, st, (const float*)ws, bias, res, out, total,
                        Cout, ksplit);
   }
   FH_LAUNCH_CHECK();
   return 0;
+}
+
+int fh_conv2d_x6_nhwc(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
+                      int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
+                      void* stream) {
+  return conv2d_x6_launch(in, false, nullptr, 0, wx, bias, res, out, ws, ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride,
+                          nullptr, stream);
+}
+
+int fh_conv2d_x6_nhwc_gn(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
+                         int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
+                         const fh_gn_epilogue* epi, void* stream) {
+  return conv2d_x6_launch(in, false, nullptr, 0, wx, bias, res, out, ws, ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride,
+                          epi, stream);
 }
 
 // A[n][c] = rstd * gamma * (1 + scale), B[n][c] = (beta - mean * rstd * gamma) * (1 + scale) + shift: exactly k_gn_stream's
@@ -1872,69 +1915,21 @@ int fh_groupnorm_table(const float* stats, const float* gamma, const float* beta
 
 // 1 when fh_conv2d_x6_norm_nhwc supports the layer (the row-reuse tiling must apply and fill the chip)
 int fh_conv2d_x6_norm_supported(int N, int H, int W, int Cin, int Cout) {
-  const int64_t M = (int64_t)N * H * W;
-  if (Cin < kBK || Cin % kBK != 0 || Cout <= 64 || M % 128 != 0) return 0;
-  if (((M + 127) / 128) * ((Cout + 127) / 128) < 384) return 0;
-  return (W % 128 == 0) || (W == 64 && H % 2 == 0) || (W == 32 && H % 4 == 0);
+  if (N < 1 || H < 1 || W < 1 || Cin < kBK || Cin % kBK != 0 || Cout < 1) return 0;
+  return x6_plan(1, N, H, W, Cin, Cout, 3, 3, 1, 1, true).reuse;
 }
-
-static int conv2d_x6_norm_impl(const float* in, const float* ab_table, int act, const void* wx, const float* bias,
-                               const float* res, float* out, int N, int H, int W, int Cin, int Cout, const fh_gn_epilogue* epi,
-                               void* stream);
 
 int fh_conv2d_x6_norm_nhwc(const float* in, const float* ab_table, int act, const void* wx, const float* bias,
                            const float* res, float* out, int N, int H, int W, int Cin, int Cout, void* stream) {
-  return conv2d_x6_norm_impl(in, ab_table, act, wx, bias, res, out, N, H, W, Cin, Cout, nullptr, stream);
+  return conv2d_x6_launch(in, true, ab_table, act, wx, bias, res, out, nullptr, 1, N, H, W, Cin, Cout, 3, 3, 1, 1, nullptr,
+                          stream);
 }
 
 int fh_conv2d_x6_norm_nhwc_gn(const float* in, const float* ab_table, int act, const void* wx, const float* bias,
                               const float* res, float* out, int N, int H, int W, int Cin, int Cout, const fh_gn_epilogue* epi,
                               void* stream) {
-  return conv2d_x6_norm_impl(in, ab_table, act, wx, bias, res, out, N, H, W, Cin, Cout, epi, stream);
-}
-
-static int conv2d_x6_norm_impl(const float* in, const float* ab_table, int act, const void* wx, const float* bias,
-                               const float* res, float* out, int N, int H, int W, int Cin, int Cout, const fh_gn_epilogue* epi,
-                               void* stream) {
-  if (!in || !ab_table || !wx || !out || !fh_conv2d_x6_norm_supported(N, H, W, Cin, Cout)) return FH_EINVAL;
-  ConvArgsX a;
-  a.ab = ab_table, a.act = act;
-  {
-    // the fused-input kernel takes the same tile as the plain 3 x 3 / stride 1 / pad 1 launch of the layer
-    const int rc = set_gn(a, epi, fh_conv2d_x6_gn_chunks(1, N, H, W, Cin, Cout, 3, 3, 1, 1));
-    if (rc) return rc;
-  }
-  a.in = in, a.wx = (const __bf16*)wx, a.bias = bias, a.res = res, a.out = out;
-  a.N = N, a.H = H, a.W = W, a.Cin = Cin, a.Cout = Cout, a.KH = 3, a.KW = 3, a.pad = 1, a.stride = 1;
-  a.Ho = H, a.Wo = W, a.ksplit = 1, a.ws = nullptr;
-  const int64_t M = (int64_t)N * H * W;
-  const dim3 grid((unsigned)(M / 128), (Cout + 127) / 128, 1);
-  hipStream_t st = (hipStream_t)stream;
-  static const int no_big = getenv("FH_X6_NOBIG") != nullptr;
-  const bool big = !no_big && M % 256 == 0 && (M / 256) * ((Cout + 127) / 128) >= 256;
-  const dim3 gbig((unsigned)(M / 256), (Cout + 127) / 128, 1);
-  static const int glds = getenv("FH_X6_GLDS") ? atoi(getenv("FH_X6_GLDS")) : 1;
-  static const int deep = getenv("FH_X6_DEEP") ? atoi(getenv("FH_X6_DEEP")) : 1;
-  if (big && glds && W % 256 == 0)
-    X6_DISPATCH((k_conv_x6r<256, true, 256, 1, true>), (k_conv_x6r<256, true, 256, 2, true>), (k_conv_x6r<256, true, 256, 3, true>), (k_conv_x6r<256, true, 256, 1, true, true>), (deep ? k_conv_x6r<256, true, 256, 2, 2, true> : k_conv_x6r<256, true, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-  else if (big && glds && W == 128 && H % 2 == 0)
-    X6_DISPATCH((k_conv_x6r<128, true, 256, 1, true>), (k_conv_x6r<128, true, 256, 2, true>), (k_conv_x6r<128, true, 256, 3, true>), (k_conv_x6r<128, true, 256, 1, true, true>), (deep ? k_conv_x6r<128, true, 256, 2, 2, true> : k_conv_x6r<128, true, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-  else if (big && glds && W == 64 && H % 4 == 0)
-    X6_DISPATCH((k_conv_x6r<64, true, 256, 1, true>), (k_conv_x6r<64, true, 256, 2, true>), (k_conv_x6r<64, true, 256, 3, true>), (k_conv_x6r<64, true, 256, 1, true, true>), (deep ? k_conv_x6r<64, true, 256, 2, 2, true> : k_conv_x6r<64, true, 256, 2, 1, true>), gbig, dim3(1024), 0, st, a);
-  else if (big && W % 256 == 0)
-    X6_DISPATCH((k_conv_x6r<256, true, 256, 1>), (k_conv_x6r<256, true, 256, 2>), (k_conv_x6r<256, true, 256, 3>), (k_conv_x6r<256, true, 256, 1, false, true>), (k_conv_x6r<256, true, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-  else if (big && W == 128 && H % 2 == 0)
-    X6_DISPATCH((k_conv_x6r<128, true, 256, 1>), (k_conv_x6r<128, true, 256, 2>), (k_conv_x6r<128, true, 256, 3>), (k_conv_x6r<128, true, 256, 1, false, true>), (k_conv_x6r<128, true, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-  else if (big && W == 64 && H % 4 == 0)
-    X6_DISPATCH((k_conv_x6r<64, true, 256, 1>), (k_conv_x6r<64, true, 256, 2>), (k_conv_x6r<64, true, 256, 3>), (k_conv_x6r<64, true, 256, 1, false, true>), (k_conv_x6r<64, true, 256, 2, false, true>), gbig, dim3(1024), 0, st, a);
-  else if (W % 128 == 0)
-    X6_DISPATCH((k_conv_x6r<128, true, 128, 1>), (k_conv_x6r<128, true, 128, 2>), (k_conv_x6r<128, true, 128, 3>), (k_conv_x6r<128, true, 128, 1, false, true>), (k_conv_x6r<128, true, 128, 2, false, true>), grid, dim3(512), 0, st, a);
-  else if (W == 64)
-    X6_DISPATCH((k_conv_x6r<64, true, 128, 1>), (k_conv_x6r<64, true, 128, 2>), (k_conv_x6r<64, true, 128, 3>), (k_conv_x6r<64, true, 128, 1, false, true>), (k_conv_x6r<64, true, 128, 2, false, true>), grid, dim3(512), 0, st, a);
-  else
-    X6_DISPATCH((k_conv_x6r<32, true, 128, 1>), (k_conv_x6r<32, true, 128, 2>), (k_conv_x6r<32, true, 128, 3>), (k_conv_x6r<32, true, 128, 1, false, true>), (k_conv_x6r<32, true, 128, 2, false, true>), grid, dim3(512), 0, st, a);
-  FH_LAUNCH_CHECK();
-  return 0;
+  return conv2d_x6_launch(in, true, ab_table, act, wx, bias, res, out, nullptr, 1, N, H, W, Cin, Cout, 3, 3, 1, 1, epi,
+                          stream);
 }
 
 int fh_conv3x3_thin_nhwc(const float* in, const float* w, const float* bias, float* out, int N, int H, int W, int Cin,

@@ -134,18 +134,8 @@ class LPIPS:
         return x
 
     def _conv(self, c, x):
-        N, H, W, Ci = x.shape
-        assert Ci == c.ci_p, (x.shape, c.ci_p)
-        out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
-        ks = self.lib.fh_conv2d_splitk(N, H, W, Ci, c.co, 3, 3)
-        ws = torch.empty(ks, N * H * W, c.co, dtype=torch.float32, device=x.device) if ks > 1 else None
-        if c.wx_f is not None and unet_hip._use_x6(N, H, W, c.co):
-            fn, wgt, what = self.lib.fh_conv2d_x6_nhwc, c.wx_f, "fh_conv2d_x6_nhwc"
-        else:
-            fn, wgt, what = self.lib.fh_conv2d_nhwc, c.wf, "fh_conv2d_nhwc"
-        _lib.check(fn(x.data_ptr(), wgt.data_ptr(), c.b.data_ptr(), None, out.data_ptr(),
-                      None if ws is None else ws.data_ptr(), ks, N, H, W, Ci, c.co, 3, 3, 1, 1, _lib.stream()), what)
-        return out
+        assert x.shape[-1] == c.ci_p, (x.shape, c.ci_p)
+        return unet_hip.conv_launch(self.lib, c, True, x, None, c.b)[0]
 
     def _relu(self, x):
         _lib.check(self.lib.fh_relu_f32(x.data_ptr(), x.numel(), _lib.stream()), "fh_relu_f32")

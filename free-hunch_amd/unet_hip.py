@@ -135,6 +135,39 @@ class _Conv:
         return self.wh_f if fwd else self.wh_d
 
 
+def conv_launch(lib, c, fwd, x, res=None, bias=None, stride=1, ops=None, mode=None, gn=None):
+    """One implicit-GEMM convolution launch of the `_Conv` c on NHWC `x`: forward weights (`fwd`) or input-gradient
+    weights.  In order: split-K factor, workspace, the split-bf16 / fp32 kernel choice, and for the split-bf16 kernel the
+    precision mode of this launch, the input's magnitude (half-split mode) and the group-sum epilogue.  `ops` is the
+    HipOps that owns the precision mode and the epilogue buffers (None: the exact split, the caller having set mode 0);
+    `mode` / `gn` are the epilogue request of `HipOps._epilogue` (mode None: the plain entry point, no epilogue).
+    Returns (output, what the epilogue left behind or None)."""
+    N, H, W, K = x.shape
+    rows, wgt32, wx = (c.co, c.wf, c.wx_f) if fwd else (c.ci, c.wd, c.wx_d)
+    what = "" if fwd else "(dgrad)"
+    pad = c.kh // 2
+    Ho, Wo = (H + 2 * pad - c.kh) // stride + 1, (W + 2 * pad - c.kw) // stride + 1
+    out = torch.empty(N, Ho, Wo, rows, dtype=torch.float32, device=x.device)
+    ks = lib.fh_conv2d_splitk(N, Ho, Wo, K, rows, c.kh, c.kw)
+    ws = torch.empty(ks, N * Ho * Wo, rows, dtype=torch.float32, device=x.device) if ks > 1 else None
+    head = (None if bias is None else bias.data_ptr(), None if res is None else res.data_ptr(), out.data_ptr(),
+            None if ws is None else ws.data_ptr(), ks, N, H, W, K, rows, c.kh, c.kw, pad, stride)
+    if wx is None or not _use_x6(N, Ho, Wo, rows):
+        _lib.check(lib.fh_conv2d_nhwc(x.data_ptr(), wgt32.data_ptr(), *head, _lib.stream()), "fh_conv2d_nhwc" + what)
+        return out, None
+    # (the forward pass never reads a tensor's recorded magnitude: its 1 x 1 layers keep the exact split)
+    m = 0 if ops is None else ops._launch_mode(c, stride, None if fwd else x)
+    wgt = c.planes(fwd, m)
+    if mode is None:
+        _lib.check(lib.fh_conv2d_x6_nhwc(x.data_ptr(), wgt.data_ptr(), *head, _lib.stream()), "fh_conv2d_x6_nhwc" + what)
+        return out, None
+    amax = ops._amax(x) if m == 4 else None
+    epi, keep = ops._epilogue(ks, N, H, W, K, rows, c.kh, c.kw, pad, mode, gn, amax=amax)
+    _lib.check(lib.fh_conv2d_x6_nhwc_gn(x.data_ptr(), wgt.data_ptr(), *head, epi, _lib.stream()),
+               "fh_conv2d_x6_nhwc" + what)
+    return out, keep
+
+
 class HipOps:
     def __init__(self, cfg, P):
         self.cfg = cfg
@@ -182,47 +215,24 @@ class HipOps:
         c = self.conv[name]
         N, H, W, Ci = x.shape
         assert Ci == c.ci_p, (name, x.shape, c.ci_p)
-        pad = c.kh // 2
         b = c.b if bias_override is None else bias_override
         if stride != 1:  # Downsample(use_conv=True), openai_unet.py:131: 3x3, stride 2, padding 1
-            Ho, Wo = (H + 2 * pad - c.kh) // stride + 1, (W + 2 * pad - c.kw) // stride + 1
-            out = torch.empty(N, Ho, Wo, c.co, dtype=torch.float32, device=x.device)
-            ks = self.lib.fh_conv2d_splitk(N, Ho, Wo, Ci, c.co, c.kh, c.kw)
-            ws = torch.empty(ks, N * Ho * Wo, c.co, dtype=torch.float32, device=x.device) if ks > 1 else None
-            fn, wgt = ((self.lib.fh_conv2d_x6_nhwc, c.planes(True, self._launch_mode(c, stride)))
-                       if c.wx_f is not None and _use_x6(N, Ho, Wo, c.co) else (self.lib.fh_conv2d_nhwc, c.wf))
-            _lib.check(fn(x.data_ptr(), wgt.data_ptr(), b.data_ptr(), None if res is None else res.data_ptr(),
-                          out.data_ptr(), None if ws is None else ws.data_ptr(), ks, N, H, W, Ci, c.co, c.kh, c.kw, pad,
-                          stride, _lib.stream()), "fh_conv2d(stride)")
-            return out
-        out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
+            return conv_launch(self.lib, c, True, x, res, b, stride, ops=self)[0]
         if c.wu_f is not None and _use_wino(N, H, W, Ci, c.co):
+            out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
             _lib.check(self.lib.fh_conv3x3_wino_nhwc(x.data_ptr(), c.wu_f.data_ptr(), b.data_ptr(),
                                                      None if res is None else res.data_ptr(), out.data_ptr(), N, H, W,
                                                      Ci, c.co, _lib.stream()), "fh_conv3x3_wino_nhwc")
             return out
         if c.co <= 8 and c.kh == 3 and c.kw == 3 and res is None and H * W >= 4096:
+            out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
             _lib.check(self.lib.fh_conv3x3_thin_nhwc(x.data_ptr(), c.wf.data_ptr(), b.data_ptr(), out.data_ptr(), N, H, W,
                                                      Ci, c.co, _lib.stream()), "fh_conv3x3_thin_nhwc")
             return out
-        ks = self.lib.fh_conv2d_splitk(N, H, W, Ci, c.co, c.kh, c.kw)
-        ws = torch.empty(ks, N * H * W, c.co, dtype=torch.float32, device=x.device) if ks > 1 else None
-        if c.wx_f is not None and _use_x6(N, H, W, c.co):
-            # group-sum epilogue: the statistics of a GroupNorm applied to this output come out of the convolution itself
-            m = self._launch_mode(c)
-            amax = self._amax(x) if m == 4 else None
-            epi, keep = self._epilogue(ks, N, H, W, Ci, c.co, c.kh, c.kw, pad, 0, amax=amax)
-            _lib.check(self.lib.fh_conv2d_x6_nhwc_gn(x.data_ptr(), c.planes(True, m).data_ptr(), b.data_ptr(),
-                                                     None if res is None else res.data_ptr(), out.data_ptr(),
-                                                     None if ws is None else ws.data_ptr(), ks, N, H, W, Ci, c.co, c.kh,
-                                                     c.kw, pad, 1, epi, _lib.stream()), "fh_conv2d_x6_nhwc")
-            if keep is not None:
-                out._fh_gn = keep
-            return out
-        _lib.check(self.lib.fh_conv2d_nhwc(x.data_ptr(), c.wf.data_ptr(), b.data_ptr(),
-                                           None if res is None else res.data_ptr(), out.data_ptr(),
-                                           None if ws is None else ws.data_ptr(), ks, N, H, W, Ci, c.co,
-                                           c.kh, c.kw, pad, 1, _lib.stream()), "fh_conv2d_nhwc")
+        # group-sum epilogue: the statistics of a GroupNorm applied to this output come out of the convolution itself
+        out, keep = conv_launch(self.lib, c, True, x, res, b, 1, ops=self, mode=0)
+        if keep is not None:
+            out._fh_gn = keep
         return out
 
     def _dgrad(self, name, g, res=None, gn=None):
@@ -235,38 +245,26 @@ class HipOps:
             gp = torch.zeros(N, H, W, c.co_p, dtype=torch.float32, device=g.device)
             gp[..., :Co] = g
             g = gp
-        out = torch.empty(N, H, W, c.ci, dtype=torch.float32, device=g.device)
         if c.wu_d is not None and _use_wino(N, H, W, c.co_p, c.ci):
+            out = torch.empty(N, H, W, c.ci, dtype=torch.float32, device=g.device)
             _lib.check(self.lib.fh_conv3x3_wino_nhwc(g.data_ptr(), c.wu_d.data_ptr(), None,
                                                      None if res is None else res.data_ptr(), out.data_ptr(), N, H, W,
                                                      c.co_p, c.ci, _lib.stream()), "fh_conv3x3_wino_nhwc(dgrad)")
             return out
         if c.ci <= 8 and c.kh == 3 and c.kw == 3 and res is None and H * W >= 4096:
+            out = torch.empty(N, H, W, c.ci, dtype=torch.float32, device=g.device)
             _lib.check(self.lib.fh_conv3x3_thin_nhwc(g.data_ptr(), c.wd.data_ptr(), None, out.data_ptr(), N, H, W, c.co_p,
                                                      c.ci, _lib.stream()), "fh_conv3x3_thin_nhwc(dgrad)")
             return out
-        ks = self.lib.fh_conv2d_splitk(N, H, W, c.co_p, c.ci, c.kh, c.kw)
-        ws = torch.empty(ks, N * H * W, c.ci, dtype=torch.float32, device=g.device) if ks > 1 else None
-        if c.wx_d is not None and _use_x6(N, H, W, c.ci):
-            m = self._launch_mode(c, 1, g)
-            amax = self._amax(g) if m == 4 else None
-            epi, keep = self._epilogue(ks, N, H, W, c.co_p, c.ci, c.kh, c.kw, c.kh // 2, 1,
-                                       gn if gn is not None and gn[1].shape == out.shape else None, amax=amax)
-            _lib.check(self.lib.fh_conv2d_x6_nhwc_gn(g.data_ptr(), c.planes(False, m).data_ptr(), None,
-                                                     None if res is None else res.data_ptr(), out.data_ptr(),
-                                                     None if ws is None else ws.data_ptr(), ks, N, H, W, c.co_p, c.ci, c.kh,
-                                                     c.kw, c.kh // 2, 1, epi, _lib.stream()), "fh_conv2d_x6_nhwc(dgrad)")
-            if keep is not None:
-                partial, chunks = keep[0], keep[1]
-                sums = torch.empty(N, 32, 2, dtype=torch.float32, device=g.device)
-                _lib.check(self.lib.fh_groupnorm_finalize(partial.data_ptr(), sums.data_ptr(), N, chunks,
-                                                          float(H * W * (c.ci // 32)), 1, _lib.stream()), "gn_finalize(1)")
-                out._fh_gn_sums = sums
-            return out
-        _lib.check(self.lib.fh_conv2d_nhwc(g.data_ptr(), c.wd.data_ptr(), None,
-                                           None if res is None else res.data_ptr(), out.data_ptr(),
-                                           None if ws is None else ws.data_ptr(), ks, N, H, W, c.co_p,
-                                           c.ci, c.kh, c.kw, c.kh // 2, 1, _lib.stream()), "fh_conv2d_nhwc(dgrad)")
+        if gn is not None and tuple(gn[1].shape) != (N, H, W, c.ci):
+            gn = None
+        out, keep = conv_launch(self.lib, c, False, g, res, None, 1, ops=self, mode=1, gn=gn)
+        if keep is not None:
+            partial, chunks = keep[0], keep[1]
+            sums = torch.empty(N, 32, 2, dtype=torch.float32, device=g.device)
+            _lib.check(self.lib.fh_groupnorm_finalize(partial.data_ptr(), sums.data_ptr(), N, chunks,
+                                                      float(H * W * (c.ci // 32)), 1, _lib.stream()), "gn_finalize(1)")
+            out._fh_gn_sums = sums
         return out
 
     def _epilogue(self, ks, N, H, W, Ci, Co, kh, kw, pad, mode, gn=None, amax=None):
