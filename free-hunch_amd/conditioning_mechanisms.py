@@ -23,10 +23,10 @@ import torch
 from torch.autograd import grad
 
 from . import _lib
-from .covariance import CovarianceHessianBFGS, CovarianceHessianBFGSDCT, ScalarCovariance, _load_cached
+from .covariance import CovarianceHessianBFGS, CovarianceHessianBFGSDCT, ScalarCovariance
+from .recon_mse import load_table
 
 F64 = torch.float64
-_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 
 
 def choose_conditioning_mechanism(name):
@@ -308,8 +308,9 @@ class BFGSOnlineUpdate(ConditioningMechanism):
         if self.solver_type == "scipy":
             raise ValueError("solver_type=scipy solves with a scalar / per-pixel variance; online_covariance needs "
                              "customcuda or customscipy")
-        # the reference loads this file unconditionally (:225-226)
-        self.recon_mse = _load_cached(os.path.join(_DATA, "recon_mse.pt"))
+        # the reference loads this file unconditionally (:225-226); recon_mse_path: the dataset's own table
+        # (python -m free_hunch_amd.recon_mse), absent = the shipped ImageNet one
+        self.recon_mse = load_table(argv.get("recon_mse_path"))
         self.mle_sigma_thres = 0.2
         self.trace = []  # per call: niter, branch, k (not in the reference; used by the parity tests)
 
@@ -520,7 +521,7 @@ class PiGDM_Videodiff_schedule(_ScalarVarianceMechanism):  # :154-171
 class PengAnalytic(_ScalarVarianceMechanism):  # :87-110
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
-        self.recon_mse = torch.load(os.path.join(_DATA, "recon_mse.pt"), weights_only=True)
+        self.recon_mse = load_table(self.argv.get("recon_mse_path"))  # absent = the shipped ImageNet table
 
     def _variance(self, sigma):
         if sigma < self.mle_sigma_thres:

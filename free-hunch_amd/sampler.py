@@ -52,7 +52,7 @@ def _make_mechanism(o, forward_operator, sigma0, data_dim):
         space_step_update_lower_threshold=o["space_step_update_lower_threshold"], max_rtol=o["max_rtol"],
         do_space_updates=o["do_space_updates"], use_analytic_var_at_end=o.get("use_analytic_var_at_end", False),
         solver_type=o.get("solver_type", "customcuda"), use_rtol_func=o.get("use_rtol_func", False),
-        diffpir_lambda=o.get("diffpir_lambda", 10.0))
+        diffpir_lambda=o.get("diffpir_lambda", 10.0), recon_mse_path=o.get("recon_mse_path"))
 
 
 def conditional_sampler(net, noise, cond_images, operator_kwargs, noise_kwargs=None, labels=None,

@@ -73,6 +73,16 @@ def main(argv=None):
         shipped = "" if data_dir == o.dataset_path else \
             " (shipped ImageNet prior: python -m free_hunch_amd.frequency_analysis --data DIR builds the dataset's own)"
         print(f"dct_variance: {os.path.join(data_dir, 'dct_variance.pt')}{shipped}", flush=True)
+    # the dataset's own denoiser-error table when it has one, else the shipped ImageNet table (recon_mse_path=None)
+    recon_path = os.path.join(o.dataset_path, "recon_mse.pt")
+    recon_path = recon_path if os.path.exists(recon_path) else None
+    reads_recon = o.conditioning_mechanism == "peng_analytic" or \
+        (o.conditioning_mechanism == "online_covariance" and o.use_analytic_var_at_end)
+    if rank == 0 and reads_recon:
+        from free_hunch_amd.recon_mse import SHIPPED
+        shipped = "" if recon_path else \
+            " (shipped ImageNet table: python -m free_hunch_amd.recon_mse --data DIR builds the dataset's own)"
+        print(f"recon_mse: {recon_path or SHIPPED}{shipped}", flush=True)
     # every option the reference forwards to its sampler / plugin (generate_conditional.py:121-130, 495)
     kw = dict(conditioning_mechanism=o.conditioning_mechanism, cond_scaling=o.cond_scaling, clip_x0_mean=o.clip_x0_mean,
               pigdm_posthoc_scaling=o.pigdm_posthoc_scaling, max_vector_count=o.max_vector_count, dataset_path=data_dir,
@@ -82,7 +92,8 @@ def main(argv=None):
               project_to_diagonal=o.project_to_diagonal, space_step_update_threshold=o.space_step_update_threshold,
               space_step_update_lower_threshold=o.space_step_update_lower_threshold, max_rtol=o.max_rtol,
               do_space_updates=o.do_space_updates, use_analytic_var_at_end=o.use_analytic_var_at_end,
-              solver_type=o.solver_type, use_rtol_func=o.use_rtol_func, diffpir_lambda=o.diffpir_lambda)
+              solver_type=o.solver_type, use_rtol_func=o.use_rtol_func, diffpir_lambda=o.diffpir_lambda,
+              recon_mse_path=recon_path)
     loop = dict(num_steps=o.num_steps, sigma_min=o.sigma_min, sigma_max=o.sigma_max, rho=o.rho, solver=o.solver,
                 discretization=o.discretization, schedule=o.schedule, scaling=o.scaling)
     churn = dict(S_churn=o.S_churn, S_min=o.S_min, S_max=o.S_max, S_noise=o.S_noise)

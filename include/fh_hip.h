@@ -492,6 +492,25 @@ int64_t fh_lpips_tap_scratch_doubles(int N);
 int fh_lpips_tap(const float* feat, const float* lin, int N, int H, int W, int C, double* scratch, double* out,
                  int out_stride, void* stream);
 
+/* The per-sigma denoiser-error table (free-hunch_amd/recon_mse.py: the producer of recon_mse.pt) - the two kernels around the
+ * denoiser call.  x32 = u8 / 127.5 - 1 in float32, as the sampler encodes its images.  S even, 2 <= S <= 16384, n >= 1;
+ * imgs 4-byte, out and D 16-byte aligned (else FH_EINVAL).
+ *   fh_noisy_u8: out [n][3][S][S] float32 = fl32((double)x32 + sigma * eps) of imgs uint8 [n][3][S][S]: formed in float64,
+ *                rounded once.  eps is Philox4x32-10 (multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85)
+ *                with key (seed low word, seed high word) and counter (element offset inside the image / 4, img_index[b],
+ *                level, 0); its words r0..r3 give the quad's four normals by Box-Muller in float64, u = (r + 0.5) 2^-32,
+ *                (z0, z1) = sqrt(-2 ln u0) (cos 2 pi u1, sin 2 pi u1), (z2, z3) likewise from (u2, u3).  The noise of one
+ *                (seed, image, level, element) therefore does not depend on n or on the image's slot.  img_index is a HOST
+ *                array of n global image indices, each in [0, 2^32) (else FH_EINVAL); sigma >= 0, level >= 0.
+ *   fh_sqerr_u8: out[b] = sum ((double)D - (double)x32)^2 over image b, D float32 [n][3][S][S].  One workgroup per fixed chunk
+ *                of one image writes one partial, a second kernel adds an image's chunks in index order: no atomics, and the
+ *                chunking depends on S alone, so an image's sum is bitwise the same at any n and in any slot.  n <= 65535.
+ *                scratch: fh_sqerr_u8_scratch_doubles(n, S) doubles. */
+int fh_noisy_u8(const uint8_t* imgs, const int64_t* img_index, int n, int S, double sigma, int level, uint64_t seed, float* out,
+                void* stream);
+int64_t fh_sqerr_u8_scratch_doubles(int n, int S);
+int fh_sqerr_u8(const float* D, const uint8_t* imgs, int n, int S, double* scratch, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
