@@ -79,6 +79,7 @@ _SIGS = {
     "fh_read_scalars": ([C.c_void_p, c_dp, C.POINTER(C.c_double), C.c_int, C.c_void_p], C.c_int),
     "fh_conv_circ": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p], C.c_int),
+    "fh_conv_circ_plan": ([C.c_int] * 6 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_channel_mix": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_amm": ([C.c_void_p, C.POINTER(FhProblem), c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_dense_matvec_scratch_doubles": ([C.c_int, C.c_int64], C.c_int64),

@@ -366,11 +366,51 @@ __global__ __launch_bounds__(256) void k_dct_moments(const double* __restrict__ 
   *reinterpret_cast<double2*>(sumsq + k) = q;
 }
 
-// Two dense S x S passes over `planes` images: T = X b_w^T (along W), out = b_h T (along H) [+ add_scale * add].
-// b_w = b_h = the DCT basis (or its transpose) gives the 2-D DCT-II / DCT-III; a separable blur folded into the bases
+// the two dense launches at one tile size (32 TM x 32 TN per workgroup): pass 1 along W over all planes at once,
+// T[r][k] = sum_n X[r][n] * b1[k][n];  pass 2 along H per plane, Y[k][w] = sum_n b2[k][n] * T[n][w] (+ add_scale * add)
+template <int TM, int TN, int PPI>
+static void dct_bases_pair(fh_context* ctx, hipStream_t st, const double* b1, const double* b2, const double* in, double* out,
+                           int planes, const fh_cg_state* states, const double* add, double add_scale) {
+  const int S = ctx->S;
+  const unsigned gx = (S + 32 * TN - 1) / (32 * TN);
+  hipLaunchKernelGGL((k_gemm_f64<true, TM, TN, PPI>), dim3(gx, (planes * S + 32 * TM - 1) / (32 * TM), 1), dim3(256), 0, st, in, b1,
+                     ctx->tmp_img, planes * S, S, S, S, S, S, (int64_t)0, (int64_t)0, (int64_t)0, states, S,
+                     (const double*)nullptr, 0.0);
+  hipLaunchKernelGGL((k_gemm_f64<false, TM, TN, PPI>), dim3(gx, (S + 32 * TM - 1) / (32 * TM), planes), dim3(256), 0, st, b2,
+                     (const double*)ctx->tmp_img, out, S, S, S, S, S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states,
+                     1 << 30, add, add_scale);
+}
+
+// Two dense S x S passes over `planes` images: T = X b1^T (along W), out = b2 T (along H) [+ add_scale * add].
+// b1 = b2 = the DCT basis (or its transpose) gives the 2-D DCT-II / DCT-III; a separable blur folded into the bases
 // (fh_problem.fold_*) makes the same two passes compute dct2(A^T x) or A(idct2(x)).
-static int dct2d_launch_bases(fh_context* ctx, const double* in, double* out, int planes, const double* b_w, const double* b_h,
-                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st, int ppi = 3);
+static int dct2d_launch_bases(fh_context* ctx, const double* in, double* out, int planes, const double* b1, const double* b2,
+                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st, int ppi = 3) {
+  const int S = ctx->S;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  if (ppi != 1 && ppi != 3) return FH_EINVAL;
+  // Tile choice by workgroup count (256 CUs, the GEMMs are MFMA-bound: what matters is an even number of tile-units per
+  // CU).  64x64 tiles halve the LDS/global traffic per flop but S = 256, 24 planes gives 384 of them = 1.5 per CU
+  // (half the CUs carry two: 24 us); 64x32 tiles give 768 = exactly 3 half-size units per CU.
+  // One plane per image (colorization): the 32 x 32 tiles (the smallest: a batch has few planes here; not tuned).
+  const int64_t n64 = (int64_t)((S + 63) / 64) * ((S + 63) / 64) * planes;
+  const int tile = ppi == 1 ? 0 : (n64 >= 1024 ? 1 : ((int64_t)((S + 31) / 32) * ((S + 63) / 64) * planes >= 512 ? 2 : 3));
+  switch (tile) {
+    case 0: dct_bases_pair<1, 1, 1>(ctx, st, b1, b2, in, out, planes, states, add, add_scale); break;
+    case 1: dct_bases_pair<2, 2, 3>(ctx, st, b1, b2, in, out, planes, states, add, add_scale); break;
+    case 2: dct_bases_pair<2, 1, 3>(ctx, st, b1, b2, in, out, planes, states, add, add_scale); break;
+    default: dct_bases_pair<1, 1, 3>(ctx, st, b1, b2, in, out, planes, states, add, add_scale);
+  }
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
+// whether the 2-D DCT of this context runs on the symmetric half-basis passes (k_dct_sym); FH_DCT_NOSYM=1 keeps the dense
+// passes (A/B switch, read once per process)
+static bool sym_dct(const fh_context* ctx) {
+  static const bool no_sym = getenv("FH_DCT_NOSYM") != nullptr;
+  return ctx->sym_fwd != nullptr && !no_sym;
+}
 
 // the two launches of a symmetric 2-D pass: along W into the context's intermediate, then along H with the epilogue operands
 template <bool INV, int PPI>
@@ -401,18 +441,6 @@ static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int 
   if (gz < 1) gz = 1;
   if (H % 64 != 0) return FH_ESIZE;  // K chunks of 64
   const size_t lds = ((size_t)2 * 32 * (H + 2) + (size_t)2 * 2 * 32 * 66) * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 140 * 1024));
-    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 140 * 1024));
-    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<false, 1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_dct_sym<true, 1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    attr_set = true;
-  }
   const dim3 grid(gx, gy, gz);
   fh_diag_tab dg;
   memset(&dg, 0, sizeof(dg));
@@ -420,13 +448,9 @@ static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int 
     for (int i = 0; i < diag->nimg && i < FH_MAX_BATCH; ++i) dg.D[i] = diag->D[i];
   if (add == nullptr || ppi * gx * gy > 256) dot_part = nullptr;  // (the consumer sums <= 256 partials per image)
   if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? ppi * gx * gy : 0;
-  if (ppi == 1) {  // one plane per image: the same two passes, image = plane
-    if (inverse) dct_sym_pair<true, 1>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
-    else dct_sym_pair<false, 1>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
-  } else {
-    if (inverse) dct_sym_pair<true, 3>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
-    else dct_sym_pair<false, 3>(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
-  }
+  const auto pair = ppi == 1 ? (inverse ? dct_sym_pair<true, 1> : dct_sym_pair<false, 1>)  // (one plane per image: image = plane)
+                            : (inverse ? dct_sym_pair<true, 3> : dct_sym_pair<false, 3>);
+  pair(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
   FH_LAUNCH_CHECK();
   return 0;
 }
@@ -434,68 +458,13 @@ static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int 
 static int dct2d_launch(fh_context* ctx, const double* in, double* out, int planes, int inverse,
                         const fh_cg_state* states, hipStream_t st, int ppi = 3, const double* add = nullptr,
                         double add_scale = 0.0, double* dot_part = nullptr, int dot_stride = 0, int* dot_nparts = nullptr) {
-  static const bool no_sym = getenv("FH_DCT_NOSYM") != nullptr;  // A/B switch: the dense passes
-  if (ctx->sym_fwd != nullptr && !no_sym) {
+  if (sym_dct(ctx)) {
     const double* sb = inverse ? ctx->sym_inv : ctx->sym_fwd;
     return dct2d_launch_sym(ctx, in, out, planes, sb, sb, inverse, add, add_scale, states, st, nullptr, dot_part, dot_stride,
                             dot_nparts, ppi);
   }
   const double* b1 = inverse ? ctx->basis_t : ctx->basis;
   return dct2d_launch_bases(ctx, in, out, planes, b1, b1, add, add_scale, states, st, ppi);
-}
-
-static int dct2d_launch_bases(fh_context* ctx, const double* in, double* out, int planes, const double* b1, const double* b2,
-                              const double* add, double add_scale, const fh_cg_state* states, hipStream_t st, int ppi) {
-  const int S = ctx->S;
-  if (planes > ctx->planes_max) return FH_ESIZE;
-  if (ppi == 1) {  // one plane per image (colorization): the 32 x 32 tiles (the smallest: a batch has few planes here; not tuned)
-    dim3 g1((S + 31) / 32, (planes * S + 31) / 32, 1);
-    hipLaunchKernelGGL((k_gemm_f64<true, 1, 1, 1>), g1, dim3(256), 0, st, in, b1, ctx->tmp_img, planes * S, S, S, S, S, S,
-                       (int64_t)0, (int64_t)0, (int64_t)0, states, S, (const double*)nullptr, 0.0);
-    dim3 g2((S + 31) / 32, (S + 31) / 32, planes);
-    hipLaunchKernelGGL((k_gemm_f64<false, 1, 1, 1>), g2, dim3(256), 0, st, b2, (const double*)ctx->tmp_img, out, S, S, S, S,
-                       S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states, 1 << 30, add, add_scale);
-    FH_LAUNCH_CHECK();
-    return 0;
-  }
-  if (ppi != 3) return FH_EINVAL;
-  // Tile choice by workgroup count (256 CUs, the GEMMs are MFMA-bound: what matters is an even number of tile-units per
-  // CU).  64x64 tiles halve the LDS/global traffic per flop but S = 256, 24 planes gives 384 of them = 1.5 per CU
-  // (half the CUs carry two: 24 us); 64x32 tiles give 768 = exactly 3 half-size units per CU.
-  static const int force = getenv("FH_DCT_TILE") ? atoi(getenv("FH_DCT_TILE")) : 0;  // 1: 64x64, 2: 64x32, 3: 32x32
-  const int64_t n64 = (int64_t)((S + 63) / 64) * ((S + 63) / 64) * planes;
-  int tile = n64 >= 1024 ? 1 : ((int64_t)((S + 31) / 32) * ((S + 63) / 64) * planes >= 512 ? 2 : 3);
-  if (force) tile = force;
-  // pass 1 (along W): T[r][k] = sum_n X[r][n] * b1[k][n]
-  if (tile == 1) {
-    dim3 grid((S + 63) / 64, (planes * S + 63) / 64, 1);
-    hipLaunchKernelGGL((k_gemm_f64<true, 2, 2>), grid, dim3(256), 0, st, in, b1, ctx->tmp_img, planes * S, S, S, S, S, S,
-                       (int64_t)0, (int64_t)0, (int64_t)0, states, S, (const double*)nullptr, 0.0);
-  } else if (tile == 2) {
-    dim3 grid((S + 31) / 32, (planes * S + 63) / 64, 1);
-    hipLaunchKernelGGL((k_gemm_f64<true, 2, 1>), grid, dim3(256), 0, st, in, b1, ctx->tmp_img, planes * S, S, S, S, S, S,
-                       (int64_t)0, (int64_t)0, (int64_t)0, states, S, (const double*)nullptr, 0.0);
-  } else {
-    dim3 grid((S + 31) / 32, (planes * S + 31) / 32, 1);
-    hipLaunchKernelGGL((k_gemm_f64<true, 1, 1>), grid, dim3(256), 0, st, in, b1, ctx->tmp_img, planes * S, S, S, S, S, S,
-                       (int64_t)0, (int64_t)0, (int64_t)0, states, S, (const double*)nullptr, 0.0);
-  }
-  // pass 2 (along H), per plane: Y[k][w] = sum_n b1[k][n] * T[n][w]
-  if (tile == 1) {
-    dim3 grid((S + 63) / 64, (S + 63) / 64, planes);
-    hipLaunchKernelGGL((k_gemm_f64<false, 2, 2>), grid, dim3(256), 0, st, b2, (const double*)ctx->tmp_img, out, S, S, S, S,
-                       S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states, 1 << 30, add, add_scale);
-  } else if (tile == 2) {
-    dim3 grid((S + 31) / 32, (S + 63) / 64, planes);
-    hipLaunchKernelGGL((k_gemm_f64<false, 2, 1>), grid, dim3(256), 0, st, b2, (const double*)ctx->tmp_img, out, S, S, S, S,
-                       S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states, 1 << 30, add, add_scale);
-  } else {
-    dim3 grid((S + 31) / 32, (S + 31) / 32, planes);
-    hipLaunchKernelGGL((k_gemm_f64<false, 1, 1>), grid, dim3(256), 0, st, b2, (const double*)ctx->tmp_img, out, S, S, S, S,
-                       S, S, (int64_t)0, (int64_t)S * S, (int64_t)S * S, states, 1 << 30, add, add_scale);
-  }
-  FH_LAUNCH_CHECK();
-  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1392,14 +1361,59 @@ __global__ __launch_bounds__(256) void k_bfgs_inverse_commit(PtrTab scalt, PtrTa
 }
 
 // ------------------------------------------------------------------------------------------------
-// Circular convolution with a sparse tap list.
+// Circular convolution with a sparse tap list.  conv_plan (after the kernels) is the one place that chooses among the seven
+// kernels - k_conv1d<0/1>, k_conv_tile8, k_conv_tile, k_conv_dec, k_conv_up, k_conv_direct - and sizes their launches.
 //   k_conv_tile   : stride-1 output grid (blur, blur^T, and blur^T of a zero-inserted LR image):
 //                   16x32 output tile + halo staged in LDS (<= 56 KiB at halo 30), 2 outputs per
 //                   thread, taps read through the scalar path (uniform index).
 //   k_conv_direct : decimated forward (SR: out[i][j] sampled at (i*stride, j*stride)).
 // Epilogue: out = acc + add_scale * add  when add != null  (the sigma_y^2 u term of A_mm).
+// The dynamic LDS of each kernel is laid out by ONE *_lds struct: the kernel carves its regions from it and conv_plan sizes
+// the launch from the same constructor (extents and offsets in doubles, `bytes` = the whole allocation).
 // ------------------------------------------------------------------------------------------------
 constexpr int kMaxTaps = 1024;
+constexpr int kT8W = 32, kT8H = 64;  // k_conv_tile8's output tile
+constexpr int k1dR = 8;              // k_conv1d: outputs per thread along the filter axis
+constexpr int k1dTB = 16;            //           taps per register block
+constexpr int k1dAcross = 64;        //           lanes across the filter axis
+constexpr int k1dAlong = 32;         //           outputs along the filter axis per workgroup (4 waves x 8)
+
+struct conv_tile_lds {  // [sh][sw] tile | [ntaps] weights | [ntaps] int offsets;  hy = rows (dy extent), hx = columns (dx extent)
+  int sw, sh, w_off;
+  size_t bytes;
+  __host__ __device__ conv_tile_lds(int hy, int hx, int ntaps)
+      : sw(32 + 2 * hx), sh(16 + 2 * hy), w_off(sw * sh), bytes((size_t)w_off * sizeof(double) + (size_t)ntaps * 12) {}
+};
+struct conv_tile8_lds {  // [sh][sw] tile (+1 to an even count) | [ntaps] (weight, offset) pairs
+  int sw, sh, tap_off;
+  size_t bytes;
+  __host__ __device__ conv_tile8_lds(int hy, int hx, int ntaps)
+      : sw(kT8W + 2 * hx), sh(kT8H + 2 * hy), tap_off((sw * sh + 1) & ~1), bytes((size_t)tap_off * sizeof(double) + (size_t)ntaps * 16) {}
+};
+struct conv_dec_lds {  // [s][R][Wp] input tile by column phase | [ntaps] (weight, offset) pairs
+  int hq, R, Wp, tap_off;
+  size_t bytes;
+  __host__ __device__ conv_dec_lds(int s, int hy, int hx, int ntaps)
+      : hq((hx + s - 1) / s), R(15 * s + 1 + 2 * hy), Wp(16 + 2 * hq + 1), tap_off((s * R * Wp + 1) & ~1),
+        bytes((size_t)tap_off * sizeof(double) + (size_t)ntaps * 16) {}
+};
+struct conv_up_lds {  // [s*s][cap] (weight, offset) | [Hu][Wu] tile of u | [T][SW] outputs;  cap >= taps of one phase (cap_for)
+  int hqy, hqx, Hu, Wu, T, SW, utile_off, utile_len;
+  size_t bytes;
+  static int cap_for(int s, int hy, int hx) { return ((2 * hy + s) / s + 1) * ((2 * hx + s) / s + 1); }
+  __host__ __device__ conv_up_lds(int s, int hy, int hx, int cap)
+      : hqy((hy + s - 1) / s), hqx((hx + s - 1) / s), Hu(16 + 2 * hqy), Wu(16 + 2 * hqx + 1), T(16 * s), SW(T + 1),
+        utile_off(2 * s * s * cap), utile_len((Hu * Wu + 1) & ~1), bytes(((size_t)utile_off + utile_len + (size_t)T * SW) * sizeof(double)) {}
+};
+// [span][ld] tile | [nblk * 16 + 8] dense coefficients, zero padded.  (k_conv1d<1> turns its results through the dead tile as
+// [64][33] doubles, which fits from h = 1 on: conv_plan sends h = 0 to k_conv1d<0>, which stores straight from registers.)
+struct conv1d_lds {
+  int span, ld, nblk, e_off;
+  size_t bytes;
+  __host__ __device__ explicit conv1d_lds(int h)
+      : span(k1dAlong + 2 * h), ld(k1dAcross + 1), nblk((2 * h + 1 + k1dTB - 1) / k1dTB), e_off(span * ld),
+        bytes(((size_t)e_off + nblk * k1dTB + k1dR) * sizeof(double)) {}
+};
 
 __global__ __launch_bounds__(256) void k_conv_tile(const double* __restrict__ in, double* __restrict__ out,
                                                    const int* __restrict__ tdy, const int* __restrict__ tdx,
@@ -1407,9 +1421,10 @@ __global__ __launch_bounds__(256) void k_conv_tile(const double* __restrict__ in
                                                    int halo_x, int adjoint, int up, const double* __restrict__ add,
                                                    double add_scale, const fh_cg_state* __restrict__ states) {
   IMG_GUARD(states, blockIdx.z / 3);
-  extern __shared__ __align__(16) double tile[];  // [sh*sw] tile | [ntaps] weights | [ntaps] int offsets
-  const int sw = 32 + 2 * halo_x, sh = 16 + 2 * halo;  // halo = rows (dy extent), halo_x = columns (dx extent)
-  double* s_w = tile + sw * sh;
+  extern __shared__ __align__(16) double tile[];
+  const conv_tile_lds L(halo, halo_x, ntaps);
+  const int sw = L.sw, sh = L.sh;
+  double* s_w = tile + L.w_off;
   int* s_off = reinterpret_cast<int*>(s_w + ntaps);
   const int plane = blockIdx.z;
   const int oy0 = blockIdx.y * 16, ox0 = blockIdx.x * 32;
@@ -1475,17 +1490,16 @@ __global__ __launch_bounds__(256) void k_conv_tile(const double* __restrict__ in
 // the LDS instruction rate (10 % of the f64 FMA rate on the 217-tap motion PSF); here a tap costs one 16-byte broadcast
 // read (weight + offset packed) and four two-address reads for 8 multiply-adds, and the halo is amortised over 4x the
 // outputs (2.9x the tile instead of 6.9x at the motion PSF's 58 x 16 extent).  Same tap order per output: same result.
-constexpr int kT8W = 32, kT8H = 64;
-
 __global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ in, double* __restrict__ out,
                                                     const int* __restrict__ tdy, const int* __restrict__ tdx,
                                                     const double* __restrict__ tw, int ntaps, int S, int halo,
                                                     int halo_x, int adjoint, const double* __restrict__ add,
                                                     double add_scale, const fh_cg_state* __restrict__ states) {
   IMG_GUARD(states, blockIdx.z / 3);
-  extern __shared__ __align__(16) double tile[];  // [sh*sw (+1)] tile | [ntaps] (weight, offset) pairs
-  const int sw = kT8W + 2 * halo_x, sh = kT8H + 2 * halo;
-  double2* s_tap = reinterpret_cast<double2*>(tile + ((sw * sh + 1) & ~1));
+  extern __shared__ __align__(16) double tile[];
+  const conv_tile8_lds L(halo, halo_x, ntaps);
+  const int sw = L.sw, sh = L.sh;
+  double2* s_tap = reinterpret_cast<double2*>(tile + L.tap_off);
   const int plane = blockIdx.z;
   const int oy0 = blockIdx.y * kT8H, ox0 = blockIdx.x * kT8W;
   const double* src = in + (int64_t)plane * S * S;
@@ -1580,10 +1594,12 @@ __global__ __launch_bounds__(256) void k_conv_dec(const double* __restrict__ in,
                                                   const double* __restrict__ add, double add_scale,
                                                   const fh_cg_state* __restrict__ states) {
   IMG_GUARD(states, blockIdx.z / 3);
-  extern __shared__ __align__(16) double tile[];  // [s][R][Wp] input tile by column phase | [ntaps] (weight, offset)
-  const int So = S / s, hq = (hx + s - 1) / s, hx4 = hq * s;
-  const int R = 15 * s + 1 + 2 * hy, Wp = 16 + 2 * hq + 1;
-  double2* s_tap = reinterpret_cast<double2*>(tile + ((s * R * Wp + 1) & ~1));
+  extern __shared__ __align__(16) double tile[];
+  const int So = S / s;
+  const conv_dec_lds L(s, hy, hx, ntaps);
+  const int hq = L.hq, hx4 = hq * s;
+  const int R = L.R, Wp = L.Wp;
+  double2* s_tap = reinterpret_cast<double2*>(tile + L.tap_off);
   const int plane = blockIdx.z, oy0 = blockIdx.y * 16, ox0 = blockIdx.x * 16;
   const double* src = in + (int64_t)plane * S * S;
   for (int t = threadIdx.x; t < ntaps; t += 256) {
@@ -1626,12 +1642,14 @@ __global__ __launch_bounds__(256) void k_conv_up(const double* __restrict__ in, 
                                                  int cap, const double* __restrict__ add, double add_scale,
                                                  const fh_cg_state* __restrict__ states) {
   IMG_GUARD(states, blockIdx.z / 3);
-  extern __shared__ __align__(16) double lds_up[];  // [s*s][cap] (weight, offset) | [Hu][Wu] tile of u | [16 s][16 s + 1] outputs
-  const int Sin = S / s, hqy = (hy + s - 1) / s, hqx = (hx + s - 1) / s;
-  const int Hu = 16 + 2 * hqy, Wu = 16 + 2 * hqx + 1, T = 16 * s, SW = T + 1;
+  extern __shared__ __align__(16) double lds_up[];
+  const int Sin = S / s;
+  const conv_up_lds L(s, hy, hx, cap);
+  const int hqy = L.hqy, hqx = L.hqx;
+  const int Hu = L.Hu, Wu = L.Wu, T = L.T, SW = L.SW;
   double2* lists = reinterpret_cast<double2*>(lds_up);
-  double* utile = lds_up + 2 * s * s * cap;
-  double* stage = utile + ((Hu * Wu + 1) & ~1);
+  double* utile = lds_up + L.utile_off;
+  double* stage = utile + L.utile_len;
   __shared__ int cnt_s[kUpMaxPhases];
   const int plane = blockIdx.z, tid = threadIdx.x;
   const double* src = in + (int64_t)plane * Sin * Sin;
@@ -1882,11 +1900,6 @@ __global__ __launch_bounds__(256) void k_woodbury_inner(PtrTab Msrct, int lds_, 
 // The tap list (ascending offsets, possibly with gaps) is expanded to a dense, zero-padded coefficient array in LDS:
 // e[k + h] multiplies in[p + k]; forward uses k = -offset, adjoint k = +offset (as k_conv_tile).
 // ------------------------------------------------------------------------------------------------
-constexpr int k1dR = 8;        // outputs per thread along the filter axis
-constexpr int k1dTB = 16;      // taps per register block
-constexpr int k1dAcross = 64;  // lanes across the filter axis
-constexpr int k1dAlong = 32;   // outputs along the filter axis per workgroup (4 waves x 8)
-
 template <int AXIS>
 __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, double* __restrict__ out,
                                                 const int* __restrict__ toff, const double* __restrict__ tw,
@@ -1894,11 +1907,12 @@ __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, d
                                                 double add_scale, const fh_cg_state* __restrict__ states) {
   IMG_GUARD(states, blockIdx.z / 3);
   extern __shared__ __align__(16) double lds1d[];
-  const int span = k1dAlong + 2 * h;                   // staged extent along the filter axis
-  const int ld = k1dAcross + 1;                        // row pitch (doubles)
-  double* tile = lds1d;                                // [span][ld]
-  const int nblk = (2 * h + 1 + k1dTB - 1) / k1dTB;
-  double* e = tile + span * ld;                        // [nblk * 16 + 8] dense coefficients, zero padded
+  const conv1d_lds L(h);
+  const int span = L.span;  // staged extent along the filter axis
+  const int ld = L.ld;      // row pitch (doubles)
+  const int nblk = L.nblk;
+  double* tile = lds1d;
+  double* e = tile + L.e_off;
   const int tid = threadIdx.x;
   const int plane = blockIdx.z;
   const double* src = in + (int64_t)plane * S * S;
@@ -1986,96 +2000,100 @@ __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, d
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launch plan of fh_conv_circ: decode the ABI's halo code, choose the kernel, size its grid and LDS.  Pure host
+// arithmetic (fh_conv_circ_plan answers from it without a device); conv_launch below only executes the plan.
+// ------------------------------------------------------------------------------------------------
+struct conv_extent {
+  int hy, hx;  // max |dy|, max |dx| the kernel stages
+  int axis;    // -1: 2-D tap list, 0: column list (all dx = 0), 1: row list (all dy = 0)
+};
+
+// halo codes: h = max(|dy|,|dx|) in 0..32;  -(h+1), h <= 99: column list;  -(h+101), h <= 32: row list;
+// 1000 + 64 hy + hx, both <= 32: both extents
+static int conv_decode(int halo, conv_extent* e) {
+  if (halo >= 1000) {
+    *e = {(halo - 1000) / 64, (halo - 1000) % 64, -1};
+    return e->hy > 32 || e->hx > 32 ? FH_EINVAL : 0;
+  }
+  if (halo < -133 || halo > 32) return FH_EINVAL;
+  if (halo >= 0) *e = {halo, halo, -1};
+  else if (halo > -101) *e = {-halo - 1, 0, 0};
+  else *e = {0, -halo - 101, 1};
+  return 0;
+}
+
+enum conv_kernel { kConv1dCol = 0, kConv1dRow, kConvTile8, kConvTile, kConvDec, kConvUp, kConvDirect };  // = fh_conv_circ_plan ids
+
+struct conv_choice {
+  int kernel;
+  dim3 grid;  // blocks of 256 threads
+  size_t lds;
+  int hy, hx, h, cap, up;  // the scalar arguments the chosen kernel takes besides the caller's
+};
+
+constexpr size_t kLdsDefault = 64 * 1024, kLdsOptIn = 100 * 1024;  // without / with the opt-in of set_kernel_attributes
+
+static int conv_plan(int S, int ntaps, conv_extent e, int planes, int stride, int adjoint, conv_choice* c) {
+  if (stride < 1 || S % stride != 0 || ntaps > kMaxTaps) return FH_EINVAL;
+  *c = {kConvDirect, dim3(1), 0, e.hy, e.hx, e.hy + e.hx, 0, adjoint ? stride : 1};
+  const auto tiles = [](int n, int t) { return (unsigned)((n + t - 1) / t); };
+  const auto pick = [c](int kernel, dim3 grid) { return c->kernel = kernel, c->grid = grid, 0; };
+  if (stride > 1 && stride <= 4 && e.axis < 0) {  // SR pair on the LDS-tiled kernels when the sizes allow
+    if (!adjoint && (S / stride) % 16 == 0) {
+      c->lds = conv_dec_lds(stride, e.hy, e.hx, ntaps).bytes;
+      if (c->lds <= kLdsOptIn) return pick(kConvDec, dim3(S / stride / 16, S / stride / 16, planes));
+    }
+    if (adjoint && S % (16 * stride) == 0) {
+      c->cap = conv_up_lds::cap_for(stride, e.hy, e.hx);
+      c->lds = conv_up_lds(stride, e.hy, e.hx, c->cap).bytes;
+      if (c->lds <= kLdsOptIn) return pick(kConvUp, dim3(S / (16 * stride), S / (16 * stride), planes));
+    }
+  }
+  if (!adjoint && stride > 1) {
+    const int64_t total = (int64_t)planes * (S / stride) * (S / stride);
+    c->lds = 0;
+    return pick(kConvDirect, dim3((unsigned)((total + 255) / 256)));
+  }
+  if (e.axis >= 0 && stride == 1 && S % 2 == 0) {  // 1-D pass at full resolution: register-blocked kernel
+    c->lds = conv1d_lds(c->h).bytes;
+    if (c->lds <= kLdsDefault) {
+      // (by extent, not by axis: a row list of extent 0 is also a column list, and k_conv1d<1> needs h >= 1, see conv1d_lds)
+      if (e.hx == 0) return pick(kConv1dCol, dim3(tiles(S, k1dAcross), tiles(S, k1dAlong), planes));
+      return pick(kConv1dRow, dim3(tiles(S, k1dAlong), tiles(S, k1dAcross), planes));
+    }
+  }
+  if (stride == 1) {  // 8 outputs per thread when the 64 x 32 tile with its halo fits
+    c->lds = conv_tile8_lds(e.hy, e.hx, ntaps).bytes;
+    if (c->lds <= kLdsDefault) return pick(kConvTile8, dim3(tiles(S, kT8W), tiles(S, kT8H), planes));
+  }
+  c->lds = conv_tile_lds(e.hy, e.hx, ntaps).bytes;
+  if (c->lds > kLdsDefault) return FH_ESIZE;
+  return pick(kConvTile, dim3(tiles(S, 32), tiles(S, 16), planes));
+}
+
+static int conv_plan_halo(int S, int ntaps, int halo, int planes, int stride, int adjoint, conv_choice* c) {
+  conv_extent e;
+  const int rc = conv_decode(halo, &e);
+  return rc ? rc : conv_plan(S, ntaps, e, planes, stride, adjoint, c);
+}
+
 static int conv_launch(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
                        const double* w, int ntaps, int halo, int planes, int stride, int adjoint, const double* add,
                        double add_scale, const fh_cg_state* done, hipStream_t st) {
   const int S = ctx->S;
-  // halo encodings: h = max(|dy|,|dx|) <= 32;  -(h+1) / -(h+101): 1-D column / row tap list;  1000 + 64 hy + hx: both extents
-  int hy2 = -1, hx2 = -1;
-  if (halo >= 1000) {
-    hy2 = (halo - 1000) / 64, hx2 = (halo - 1000) % 64;
-    if (hy2 > 32 || hx2 > 32) return FH_EINVAL;
-    halo = hy2 > hx2 ? hy2 : hx2;
-  }
-  if (stride < 1 || S % stride != 0 || halo < -133 || halo > 32 || ntaps > kMaxTaps) return FH_EINVAL;
-  if (stride > 1 && stride <= 4 && halo >= 0) {  // SR pair on the LDS-tiled kernels when the sizes allow
-    const int hyq = hy2 >= 0 ? hy2 : halo, hxq = hy2 >= 0 ? hx2 : halo, s_ = stride;
-    static bool attr_sr = false;
-    if (!attr_sr) {
-      FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_dec), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   100 * 1024));
-      FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv_up), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   100 * 1024));
-      attr_sr = true;
-    }
-    if (!adjoint && (S / s_) % 16 == 0) {
-      const int hq = (hxq + s_ - 1) / s_, R = 15 * s_ + 1 + 2 * hyq, Wp = 16 + 2 * hq + 1;
-      const size_t lds = (((size_t)s_ * R * Wp + 1) & ~(size_t)1) * sizeof(double) + (size_t)ntaps * 16;
-      if (lds <= 100 * 1024) {
-        const int So = S / s_;
-        hipLaunchKernelGGL(k_conv_dec, dim3(So / 16, So / 16, planes), dim3(256), lds, st, in, out, dy, dx, w, ntaps, S, s_,
-                           hyq, hxq, add, add_scale, done);
-        FH_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    if (adjoint && S % (16 * s_) == 0) {
-      const int hqy = (hyq + s_ - 1) / s_, hqx = (hxq + s_ - 1) / s_;
-      const int cap = ((2 * hyq + s_) / s_ + 1) * ((2 * hxq + s_) / s_ + 1);  // >= taps of one phase
-      const int Hu = 16 + 2 * hqy, Wu = 16 + 2 * hqx + 1, T = 16 * s_;
-      const size_t lds = ((size_t)2 * s_ * s_ * cap + (((size_t)Hu * Wu + 1) & ~(size_t)1) + (size_t)T * (T + 1)) * sizeof(double);
-      if (lds <= 100 * 1024) {
-        hipLaunchKernelGGL(k_conv_up, dim3(S / T, S / T, planes), dim3(256), lds, st, in, out, dy, dx, w, ntaps, S, s_, hyq,
-                           hxq, cap, add, add_scale, done);
-        FH_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-  }
-  if (!adjoint && stride > 1) {
-    const int So = S / stride;
-    const int64_t total = (int64_t)planes * So * So;
-    hipLaunchKernelGGL(k_conv_direct, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, out, dy, dx, w,
-                       ntaps, S, stride, planes, add, add_scale, done);
-  } else {
-    // halo = max(|dy|,|dx|); negative values encode 1-D tap lists: -(h+1) = column kernel (dx = 0), -(h+101) = row kernel
-    int hy = halo, hx = halo;
-    if (hy2 >= 0) hy = hy2, hx = hx2;
-    if (halo <= -101) hy = 0, hx = -halo - 101;
-    else if (halo < 0) hy = -halo - 1, hx = 0;
-    if (halo < 0 && stride == 1 && S % 2 == 0) {  // 1-D pass at full resolution: register-blocked kernel
-      const int h = hy + hx;
-      const int nblk = (2 * h + 1 + k1dTB - 1) / k1dTB;
-      const size_t lds1 = ((size_t)(k1dAlong + 2 * h) * (k1dAcross + 1) + nblk * k1dTB + k1dR) * sizeof(double);
-      if (lds1 <= 64 * 1024) {
-        if (hx == 0) {
-          dim3 grid((S + k1dAcross - 1) / k1dAcross, (S + k1dAlong - 1) / k1dAlong, planes);
-          hipLaunchKernelGGL(k_conv1d<0>, grid, dim3(256), lds1, st, in, out, dy, w, ntaps, S, h, adjoint, add, add_scale,
-                             done);
-        } else {
-          dim3 grid((S + k1dAlong - 1) / k1dAlong, (S + k1dAcross - 1) / k1dAcross, planes);
-          hipLaunchKernelGGL(k_conv1d<1>, grid, dim3(256), lds1, st, in, out, dx, w, ntaps, S, h, adjoint, add, add_scale,
-                             done);
-        }
-        FH_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    if (stride == 1) {  // 8 outputs per thread when the 64 x 32 tile with its halo fits
-      const size_t lds8 = (((size_t)(kT8W + 2 * hx) * (kT8H + 2 * hy) + 1) & ~(size_t)1) * sizeof(double) + (size_t)ntaps * 16;
-      if (lds8 <= 64 * 1024) {
-        dim3 grid8((S + kT8W - 1) / kT8W, (S + kT8H - 1) / kT8H, planes);
-        hipLaunchKernelGGL(k_conv_tile8, grid8, dim3(256), lds8, st, in, out, dy, dx, w, ntaps, S, hy, hx, adjoint, add,
-                           add_scale, done);
-        FH_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-    const size_t lds = (size_t)(32 + 2 * hx) * (16 + 2 * hy) * sizeof(double) + (size_t)ntaps * 12;
-    if (lds > 64 * 1024) return FH_ESIZE;
-    dim3 grid((S + 31) / 32, (S + 15) / 16, planes);
-    hipLaunchKernelGGL(k_conv_tile, grid, dim3(256), lds, st, in, out, dy, dx, w, ntaps, S, hy, hx, adjoint,
-                       adjoint ? stride : 1, add, add_scale, done);
+  conv_choice c;
+  const int rc = conv_plan_halo(S, ntaps, halo, planes, stride, adjoint, &c);
+  if (rc) return rc;
+  const dim3 b(256);
+  switch (c.kernel) {
+    case kConv1dCol: hipLaunchKernelGGL(k_conv1d<0>, c.grid, b, c.lds, st, in, out, dy, w, ntaps, S, c.h, adjoint, add, add_scale, done); break;
+    case kConv1dRow: hipLaunchKernelGGL(k_conv1d<1>, c.grid, b, c.lds, st, in, out, dx, w, ntaps, S, c.h, adjoint, add, add_scale, done); break;
+    case kConvTile8: hipLaunchKernelGGL(k_conv_tile8, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, c.hy, c.hx, adjoint, add, add_scale, done); break;
+    case kConvTile: hipLaunchKernelGGL(k_conv_tile, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, c.hy, c.hx, adjoint, c.up, add, add_scale, done); break;
+    case kConvDec: hipLaunchKernelGGL(k_conv_dec, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, stride, c.hy, c.hx, add, add_scale, done); break;
+    case kConvUp: hipLaunchKernelGGL(k_conv_up, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, stride, c.hy, c.hx, c.cap, add, add_scale, done); break;
+    default: hipLaunchKernelGGL(k_conv_direct, c.grid, b, 0, st, in, out, dy, dx, w, ntaps, S, stride, planes, add, add_scale, done);
   }
   FH_LAUNCH_CHECK();
   return 0;
@@ -2091,8 +2109,7 @@ static std::mutex g_capture_mu;
 
 // colorization with no factor columns on the symmetric DCT passes: A C A^T is diagonal in the DCT basis (D_eff)
 static bool colorize_deff_route(const fh_context* ctx, const fh_problem* p) {
-  static const bool no_sym = getenv("FH_DCT_NOSYM") != nullptr;
-  return p->op == 3 && p->use_dct && p->m == 0 && ctx->sym_fwd != nullptr && !no_sym;
+  return p->op == 3 && p->use_dct && p->m == 0 && sym_dct(ctx);
 }
 
 // once per solve (and per fh_amm call): D_eff of every image into the context's scratch, before the first apply
@@ -2210,8 +2227,7 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     if (rc) return rc;
   }
   // w0 <- C w0  (through the DCT basis when the covariance lives there)
-  static const bool no_sym_amm = getenv("FH_DCT_NOSYM") != nullptr;
-  if (p->use_dct && p->m == 0 && ctx->sym_fwd != nullptr && !no_sym_amm) {
+  if (p->use_dct && p->m == 0 && sym_dct(ctx)) {
     // as above: the diagonal-only covariance apply inside the forward DCT's second pass
     rc = dct2d_launch_sym(ctx, w0, w1, planes, ctx->sym_fwd, ctx->sym_fwd, 0, nullptr, 0.0, states, st, &per);
     if (rc) return rc;
@@ -2404,6 +2420,17 @@ __global__ __launch_bounds__(256) void k_cg_step2(const double* __restrict__ r, 
 // ================================================================================================
 // C ABI
 // ================================================================================================
+// Every kernel of this file that needs more than 64 KiB of dynamic LDS gets its opt-in here, from fh_context_create (under
+// g_capture_mu, before any launch and outside any capture): no kernel of this file launches without a context.
+static int set_kernel_attributes() {
+  const void* const at_140k[] = {(const void*)k_dct_sym<false, 3>, (const void*)k_dct_sym<true, 3>, (const void*)k_dct_sym<false, 1>,
+                                 (const void*)k_dct_sym<true, 1>, (const void*)k_woodbury_inner};
+  for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+  for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
+    FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
+  return 0;
+}
+
 extern "C" {
 
 int fh_version(void) { return 100; }
@@ -2412,6 +2439,8 @@ int fh_context_create(fh_context** out, int S, int planes_max, int m_cap) {
   if (out == nullptr || S < 2 || S > 256 || (S & 1) || planes_max < 1 || m_cap < 0 || m_cap > FH_MAX_COLS)
     return FH_EINVAL;
   std::lock_guard<std::mutex> capture_lock(g_capture_mu);
+  const int rc_attr = set_kernel_attributes();
+  if (rc_attr) return rc_attr;
   fh_context* c = new fh_context();
   memset(c, 0, sizeof(*c));
   c->S = S;
@@ -2686,12 +2715,6 @@ static int inner_update_b(fh_context* ctx, int nimg, PtrTab Msrc, int ld_src, Pt
   if (m == 0) return 0;
   if (m > kWbMax) return FH_ESIZE;  // the caller falls back to its host path
   const size_t lds = ((size_t)m * (2 * m + 1) + 2 * (size_t)m * (m + 1) + (m <= kWbLdsMax ? 3 * (size_t)m * m : 0)) * sizeof(double);
-  static bool attr_set = false;
-  if (!attr_set) {
-    FH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_woodbury_inner),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-    attr_set = true;
-  }
   const int64_t sstride = (int64_t)4 * kWbMax * kWbMax;
   if (ctx->gpartial_elems < sstride * nimg) return FH_ESIZE;
   // ctx->gpartial: the Gram partials were reduced into G before this launch (stream order); free until the next k_gram
@@ -2932,6 +2955,18 @@ int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* 
   if (!ctx || !in || !out || !dy || !dx || !w || ntaps < 1 || planes < 1) return FH_EINVAL;
   return conv_launch(ctx, in, out, dy, dx, w, ntaps, halo, planes, stride, adjoint, nullptr, 0.0, nullptr,
                      (hipStream_t)stream);
+}
+
+int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int adjoint, int32_t out[6]) {
+  if (out == nullptr) return FH_EINVAL;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (S < 2 || S > 256 || (S & 1) || ntaps < 1 || planes < 1) return FH_EINVAL;  // as fh_context_create / fh_conv_circ
+  conv_choice c;
+  const int rc = conv_plan_halo(S, ntaps, halo, planes, stride, adjoint, &c);
+  if (rc) return rc;
+  const int32_t v[6] = {c.kernel, (int32_t)c.grid.x, (int32_t)c.grid.y, (int32_t)c.grid.z, 256, (int32_t)c.lds};
+  memcpy(out, v, sizeof(v));
+  return 0;
 }
 
 int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double* w, int nimg, int adjoint, void* stream) {

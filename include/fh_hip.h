@@ -179,9 +179,16 @@ int fh_read_scalars(fh_context* ctx, const double* scal, double* out_host, int k
  * halo = max(|dy|, |dx|) over the taps (<= 32); 1-D tap lists may pass -(h+1) (column kernel, all dx = 0) or
  * -(h+101) (row kernel, all dy = 0), 2-D lists 1000 + 64 * max|dy| + max|dx|, so that only the needed halo is staged
  * (the shipped motion PSF spans 58 x 16: a third of the square halo).
- * Equals ifft2(FB * fft2(x)).real / ifft2(conj(FB) * fft2(x)).real of the reference. */
+ * Equals ifft2(FB * fft2(x)).real / ifft2(conj(FB) * fft2(x)).real of the reference.
+ * Which of the seven kernels runs, with what grid and LDS, is decided in one place, conv_plan (csrc/fh_kernels.hip);
+ * fh_conv_circ_plan below reports that decision.  FH_EINVAL: a halo code outside the above, stride < 1 or not a divisor
+ * of S, ntaps > 1024; FH_ESIZE: the halo and tap list fit no kernel's LDS. */
 int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
                  const double* w, int ntaps, int halo, int planes, int stride, int adjoint, void* stream);
+/* The launch fh_conv_circ would make on a context of image side S, without a context or a device: returns its status and
+ * fills out = {kernel, grid x, grid y, grid z, block size, dynamic LDS bytes} (zeros on an error), kernel = 0 k_conv1d<0>,
+ * 1 k_conv1d<1>, 2 k_conv_tile8, 3 k_conv_tile, 4 k_conv_dec, 5 k_conv_up, 6 k_conv_direct. */
+int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int adjoint, int32_t out[6]);
 
 /* Channel mix of the colorization operator, measurement_utils/measurements.py:74-84 (A = mean over the colour channels,
  * here with three weights w[0..2] on the device; (1/3, 1/3, 1/3) is the reference's operator):

@@ -1,0 +1,96 @@
+"""Host-side check of fh_conv_circ's launch plan (no GPU): fh_conv_circ_plan - status, kernel, grid, block, dynamic LDS
+bytes - against tests/golden/conv_circ_plan.json, which tests/golden/make_conv_circ_plan.py recorded from the launch code
+as it stood before the dispatch was folded into conv_plan (see the table's "about")."""
+import ctypes as C
+import json
+import os
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL, ESIZE = -1, -2
+LDS_LIMIT = {"k_conv_dec": 100 * 1024, "k_conv_up": 100 * 1024}  # the two kernels with an opt-in; every other: 64 KiB
+
+
+def _lib():
+    import __graft_entry__ as g
+    g.build()
+    from free_hunch_amd import _lib
+    return _lib.load()
+
+
+def _table():
+    with open(os.path.join(ROOT, "tests", "golden", "conv_circ_plan.json")) as f:
+        t = json.load(f)
+    assert t["columns"] == ["S", "stride", "adjoint", "planes", "halo", "ntaps", "status", "kernel", "grid_x", "grid_y",
+                            "grid_z", "block", "lds_bytes"]
+    assert t["kernels"] == ["k_conv1d<0>", "k_conv1d<1>", "k_conv_tile8", "k_conv_tile", "k_conv_dec", "k_conv_up",
+                            "k_conv_direct"]
+    return t
+
+
+def _plan(lib, S, ntaps, halo, planes, stride, adjoint):
+    out = (C.c_int32 * 6)()
+    rc = lib.fh_conv_circ_plan(S, ntaps, halo, planes, stride, adjoint, out)
+    return rc, list(out)
+
+
+def test_library_reproduces_the_plan_table():
+    lib, rows = _lib(), _table()["rows"]
+    assert len(rows) >= 900
+    for S, stride, adjoint, planes, halo, ntaps, status, *want in rows:
+        rc, got = _plan(lib, S, ntaps, halo, planes, stride, adjoint)
+        assert (rc, got) == (status, want), ((S, stride, adjoint, planes, halo, ntaps), (rc, got), (status, want))
+
+
+def test_table_reaches_every_kernel_and_both_errors():
+    t = _table()
+    ok = [r for r in t["rows"] if r[6] == 0]
+    assert {r[7] for r in ok} == set(range(7))
+    assert {r[6] for r in t["rows"]} == {0, EINVAL, ESIZE}
+    assert all(r[7:] == [0] * 6 for r in t["rows"] if r[6] != 0)
+    # the four encodings of the halo code all occur among the accepted rows
+    assert any(0 <= r[4] <= 32 for r in ok) and any(-100 <= r[4] < 0 for r in ok)
+    assert any(r[4] <= -101 for r in ok) and any(r[4] >= 1000 for r in ok)
+
+
+def test_accepted_plans_fit_the_lds_their_kernel_runs_under():
+    """A condition, not a measurement: 64 KiB of dynamic LDS without an opt-in, 100 KiB for k_conv_dec / k_conv_up -
+    on the table and on what the built library answers for the same rows."""
+    lib, t = _lib(), _table()
+    for S, stride, adjoint, planes, halo, ntaps, status, kernel, _gx, _gy, _gz, block, lds in t["rows"]:
+        if status != 0:
+            continue
+        rc, got = _plan(lib, S, ntaps, halo, planes, stride, adjoint)
+        limit = LDS_LIMIT.get(t["kernels"][kernel], 64 * 1024)
+        assert block == 256 and 0 <= lds <= limit and rc == 0 and 0 <= got[5] <= limit, (S, stride, adjoint, halo, ntaps, lds)
+        assert (lds == 0) == (t["kernels"][kernel] == "k_conv_direct")
+
+
+def test_gpu_test_shapes_reach_the_kernels_they_name():
+    """Which kernel the cases of test_conv_circ_matches_a_direct_sum (tests/test_edge_cases.py) reach, forward / adjoint."""
+    import numpy as np
+    lib, names = _lib(), _table()["kernels"]
+    from free_hunch_amd.measurements import _TapList
+    import torch
+    for (S, stride, kh, kw, density), want in {
+            (64, 1, 9, 5, 0.5): ("k_conv_tile8", "k_conv_tile8"), (96, 1, 31, 7, 0.3): ("k_conv_tile8", "k_conv_tile8"),
+            (256, 1, 61, 17, 0.2): ("k_conv_tile8", "k_conv_tile8"), (64, 1, 61, 61, 0.1): ("k_conv_tile", "k_conv_tile"),
+            (64, 2, 7, 7, 1.0): ("k_conv_dec", "k_conv_up"), (96, 3, 11, 9, 1.0): ("k_conv_dec", "k_conv_up"),
+            (64, 4, 25, 25, 1.0): ("k_conv_dec", "k_conv_up"), (256, 4, 25, 25, 1.0): ("k_conv_dec", "k_conv_up"),
+            (48, 4, 25, 25, 1.0): ("k_conv_direct", "k_conv_tile"), (64, 1, 25, 1, 1.0): ("k_conv1d<0>", "k_conv1d<0>"),
+            (96, 1, 1, 61, 0.5): ("k_conv1d<1>", "k_conv1d<1>"), (64, 2, 9, 1, 1.0): ("k_conv_direct", "k_conv_tile")}.items():
+        halo = _TapList(np.ones((kh, kw)), torch.device("cpu")).halo
+        got = []
+        for adjoint in (0, 1):
+            rc, out = _plan(lib, S, max(2, int(kh * kw * density)), halo, 3, stride, adjoint)  # (about the random sets' sizes)
+            assert rc == 0
+            got.append(names[out[0]])
+        assert tuple(got) == want, ((S, stride, kh, kw, density), got, want)
+
+
+def test_plan_query_rejects_what_no_context_or_call_accepts():
+    lib = _lib()
+    for args in ((0, 9, 4, 3, 1, 0), (63, 9, 4, 3, 1, 0), (258, 9, 4, 3, 1, 0), (64, 0, 4, 3, 1, 0), (64, 9, 4, 0, 1, 0),
+                 (64, 9, 4, 3, 0, 0), (64, 9, 33, 3, 1, 0), (64, 9, 999, 3, 1, 0), (64, 9, -134, 3, 1, 0),
+                 (64, 9, 1000 + 64 * 33, 3, 1, 0), (64, 9, 1000 + 33, 3, 1, 0)):
+        assert _plan(lib, *args) == (EINVAL, [0] * 6), args
+    assert lib.fh_conv_circ_plan(64, 9, 4, 3, 1, 0, None) == EINVAL

@@ -196,24 +196,8 @@ def test_batched_cg_with_a_finished_image(dev, tmp_path):
     assert infos[1].niter == 1 and not infos[1].optimal
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("S,stride,kh,kw,density", [
-    (64, 1, 9, 5, 0.5),     # k_conv_tile8, one 64 x 32 tile per row block
-    (96, 1, 31, 7, 0.3),    # partial tiles in both directions, tall sparse PSF
-    (256, 1, 61, 17, 0.2),  # the motion PSF's extent
-    (64, 1, 61, 61, 0.1),   # halo beyond the LDS budget of the 8-output kernel: k_conv_tile
-    (64, 2, 7, 7, 1.0),     # k_conv_dec / k_conv_up at every stride the reference's SR kernels cover
-    (96, 3, 11, 9, 1.0),
-    (64, 4, 25, 25, 1.0),
-    (256, 4, 25, 25, 1.0),
-    (48, 4, 25, 25, 1.0),   # sizes the tiled SR kernels do not take: k_conv_direct / k_conv_tile
-])
-def test_conv_circ_matches_a_direct_sum(S, stride, kh, kw, density):
-    """fh_conv_circ over every kernel it dispatches to (k_conv_tile8, k_conv_tile, k_conv_dec, k_conv_up, k_conv_direct)
-    against the defining circular sums in NumPy, forward and adjoint, random non-symmetric tap sets:
-      forward  out[i][j] = sum_t w_t in[(s i - dy_t) mod S][(s j - dx_t) mod S]
-      adjoint  out[y][x] = sum_t w_t z[(y + dy_t) mod S][(x + dx_t) mod S],  z = in with s - 1 zeros inserted
-    and <A x, y> = <x, A^T y> to rounding."""
+def _conv_circ_case(S, stride, kh, kw, density):
+    """Random non-symmetric kh x kw tap set and inputs of one fh_conv_circ case, and the library's forward and adjoint."""
     import numpy as np
     from free_hunch_amd import _lib
     from free_hunch_amd.measurements import _TapList
@@ -226,6 +210,38 @@ def test_conv_circ_matches_a_direct_sum(S, stride, kh, kw, density):
     So = S // stride
     x = rng.standard_normal((3, S, S))
     u = rng.standard_normal((3, So, So))
+    xd, ud = torch.from_numpy(x).to(dev), torch.from_numpy(u).to(dev)
+    got_f = ctx.conv(xd, torch.empty(3, So, So, dtype=torch.float64, device=dev), taps, 3, stride, False)
+    got_a = ctx.conv(ud, torch.empty(3, S, S, dtype=torch.float64, device=dev), taps, 3, stride, True)
+    torch.cuda.synchronize()
+    return taps, x, u, xd, ud, got_f, got_a
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,stride,kh,kw,density", [
+    (64, 1, 9, 5, 0.5),     # k_conv_tile8, one 64 x 32 tile per row block
+    (96, 1, 31, 7, 0.3),    # partial tiles in both directions, tall sparse PSF
+    (256, 1, 61, 17, 0.2),  # the motion PSF's extent
+    (64, 1, 61, 61, 0.1),   # halo beyond the LDS budget of the 8-output kernel: k_conv_tile
+    (64, 2, 7, 7, 1.0),     # k_conv_dec / k_conv_up at every stride the reference's SR kernels cover
+    (96, 3, 11, 9, 1.0),
+    (64, 4, 25, 25, 1.0),
+    (256, 4, 25, 25, 1.0),
+    (48, 4, 25, 25, 1.0),   # sizes the tiled SR kernels do not take: k_conv_direct / k_conv_tile
+    (64, 1, 25, 1, 1.0),    # column list: k_conv1d<0>, whole tiles
+    (96, 1, 1, 61, 0.5),    # row list with gaps: k_conv1d<1>, partial tiles both ways
+    (64, 2, 9, 1, 1.0),     # 1-D code on the strided fallbacks: k_conv_direct, and k_conv_tile with zero insertion
+])
+def test_conv_circ_matches_a_direct_sum(S, stride, kh, kw, density):
+    """fh_conv_circ over every kernel it dispatches to (k_conv1d<0>, k_conv1d<1>, k_conv_tile8, k_conv_tile, k_conv_dec,
+    k_conv_up, k_conv_direct; which shape reaches which is held by tests/test_conv_circ_plan.py) against the defining
+    circular sums in NumPy, forward and adjoint, random non-symmetric tap sets:
+      forward  out[i][j] = sum_t w_t in[(s i - dy_t) mod S][(s j - dx_t) mod S]
+      adjoint  out[y][x] = sum_t w_t z[(y + dy_t) mod S][(x + dx_t) mod S],  z = in with s - 1 zeros inserted
+    and <A x, y> = <x, A^T y> to rounding."""
+    import numpy as np
+    taps, x, u, xd, ud, got_f, got_a = _conv_circ_case(S, stride, kh, kw, density)
+    So = S // stride
     dy, dx, w = taps.dy.cpu().numpy(), taps.dx.cpu().numpy(), taps.w.cpu().numpy()
     fwd = np.zeros((3, So, So))
     zi = np.zeros((3, S, S))
@@ -234,11 +250,37 @@ def test_conv_circ_matches_a_direct_sum(S, stride, kh, kw, density):
     for t in range(taps.n):
         fwd += w[t] * np.roll(x, (dy[t], dx[t]), axis=(1, 2))[:, ::stride, ::stride]
         adj += w[t] * np.roll(zi, (-dy[t], -dx[t]), axis=(1, 2))
-    xd, ud = torch.from_numpy(x).to(dev), torch.from_numpy(u).to(dev)
-    got_f = ctx.conv(xd, torch.empty(3, So, So, dtype=torch.float64, device=dev), taps, 3, stride, False)
-    got_a = ctx.conv(ud, torch.empty(3, S, S, dtype=torch.float64, device=dev), taps, 3, stride, True)
-    torch.cuda.synchronize()
     assert np.abs(got_f.cpu().numpy() - fwd).max() < 1e-12 * max(1.0, np.abs(fwd).max())
     assert np.abs(got_a.cpu().numpy() - adj).max() < 1e-12 * max(1.0, np.abs(adj).max())
     lhs, rhs = float((got_f * ud).sum()), float((xd * got_a).sum())
     assert abs(lhs - rhs) < 1e-10 * max(1.0, abs(lhs))
+
+
+# one case per kernel of fh_conv_circ (forward / adjoint), taken from the direct-sum cases above
+CONV_SHA_CASES = [
+    (64, 1, 25, 1, 1.0),    # k_conv1d<0> both ways
+    (96, 1, 1, 61, 0.5),    # k_conv1d<1> both ways
+    (64, 1, 9, 5, 0.5),     # k_conv_tile8 both ways
+    (64, 1, 61, 61, 0.1),   # k_conv_tile both ways
+    (64, 2, 7, 7, 1.0),     # k_conv_dec / k_conv_up
+    (48, 4, 25, 25, 1.0),   # k_conv_direct / k_conv_tile with zero insertion
+]
+
+
+def _conv_sha(S, stride, kh, kw, density):
+    import hashlib
+    _taps, _x, _u, _xd, _ud, got_f, got_a = _conv_circ_case(S, stride, kh, kw, density)
+    return {"forward": hashlib.sha256(got_f.cpu().numpy().tobytes()).hexdigest(),
+            "adjoint": hashlib.sha256(got_a.cpu().numpy().tobytes()).hexdigest()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S,stride,kh,kw,density", CONV_SHA_CASES)
+def test_conv_circ_is_bitwise_what_it_was(S, stride, kh, kw, density):
+    """The kernels accumulate with explicit fma in the tap list's order, so their outputs are deterministic: the SHA-256
+    of the output bytes equals what the library gave on the MI355X before the dispatch was folded into conv_plan
+    (tests/golden/conv_circ_sha.json, recorded from that build with these inputs)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "conv_circ_sha.json")) as f:
+        want = json.load(f)["sha256"]["%d-%d-%d-%d-%g" % (S, stride, kh, kw, density)]
+    assert _conv_sha(S, stride, kh, kw, density) == want
