@@ -1513,6 +1513,239 @@ __global__ __launch_bounds__(256) void k_gn_stream(const float* __restrict__ x, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// One-launch GroupNorm for small tensors (the UNet levels whose convolutions run split-K and leave no group sums).
+// Workgroup = one (image, group) slice: P pixels x cg channels, cg * 4 contiguous bytes per pixel.  A thread owns one channel
+// quad (threadIdx % q4, q4 = cg / 4, so its per-channel constants are loop-invariant) of up to IPT pixels (threadIdx / q4 +
+// k * lanes, lanes = 512 / q4) and keeps these float4 items in registers between the two sweeps: sweep 1 reduces them
+// (double; xor shuffles inside a wave, then the waves in wave order - a fixed order that does not depend on N), sweep 2
+// writes the result.  The statistics follow k_gn_finalize, the sums k_gn_partial<1>, the results k_gn_stream, expression
+// for expression.  A workgroup touches only its own slice and talks to no other workgroup, so the in-place accumulate of
+// the backward pass is safe.
+// ------------------------------------------------------------------------------------------------
+constexpr int kGnSmallThreads = 512;
+constexpr int kGnSmallMaxIpt = 16;    // float4 items a thread can hold
+// fh_groupnorm_small_supported, both measured (profiles/gn_small.md): L, the elements of a slice (what the registers of a
+// workgroup hold), and the pixels of a slice - a workgroup pays per cache line it touches, one or more per pixel, and
+// above 1024 pixels the three launches are the faster form whatever the slice holds
+constexpr int kGnSmallLimit = 32768;
+constexpr int kGnSmallMaxPixels = 1024;
+static_assert(kGnSmallLimit <= kGnSmallThreads * kGnSmallMaxIpt * 4, "a slice must fit the registers of one workgroup");
+
+__device__ __forceinline__ void gn_small_sum2(double& a, double& b, double (*red)[2]) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_xor(a, o, 64);
+    b += __shfl_xor(b, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][0] = a, red[threadIdx.x >> 6][1] = b;
+  __syncthreads();
+  a = 0.0, b = 0.0;
+#pragma unroll
+  for (int w = 0; w < kGnSmallThreads / 64; ++w) a += red[w][0], b += red[w][1];
+}
+
+template <int IPT>
+__global__ __launch_bounds__(kGnSmallThreads) void k_gn_small_fwd(const float* __restrict__ x, const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, int ss_stride,
+                                                                  float* __restrict__ y, float* __restrict__ stats, int P, int C,
+                                                                  int act) {
+  __shared__ double red[kGnSmallThreads / 64][2];
+  const int n = blockIdx.x >> 5, grp = blockIdx.x & 31;
+  const int cg = C / 32, q4 = cg / 4, lanes = kGnSmallThreads / q4;
+  const int lane = threadIdx.x / q4, j = threadIdx.x - lane * q4;
+  const int pend = lane < lanes ? P : 0;  // (the threads past lanes * q4 own nothing)
+  const int64_t base = (int64_t)n * P * C + grp * cg + 4 * j;
+  float4 xv[IPT];
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int p = lane + k * lanes;
+    xv[k] = p < pend ? *reinterpret_cast<const float4*>(x + base + (int64_t)p * C) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  double s0 = 0.0, s1 = 0.0;  // (items past the end are zeros: they add nothing)
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const float xs[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s0 += xs[e];
+      s1 += (double)xs[e] * xs[e];
+    }
+  }
+  gn_small_sum2(s0, s1, red);
+  const double count = (double)P * cg;
+  const double dmean = s0 / count;
+  double var = s1 / count - dmean * dmean;
+  var = var < 0 ? 0 : var;
+  const float mean = (float)dmean, rstd = (float)(1.0 / sqrt(var + 1e-5));
+  if (threadIdx.x == 0) stats[((int64_t)n * 32 + grp) * 2] = mean, stats[((int64_t)n * 32 + grp) * 2 + 1] = rstd;
+  float A[4], Bc[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int c = grp * cg + 4 * j + e;
+    const float sc = scale != nullptr ? 1.f + scale[(int64_t)n * ss_stride + c] : 1.f;
+    const float sh = shift != nullptr ? shift[(int64_t)n * ss_stride + c] : 0.f;
+    const float rg = rstd * gamma[c];
+    A[e] = rg * sc;
+    Bc[e] = (beta[c] - mean * rg) * sc + sh;
+  }
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int p = lane + k * lanes;
+    if (p >= pend) continue;
+    const float xs[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float t = fmaf(xs[e], A[e], Bc[e]);
+      o[e] = act ? silu_f(t) : t;
+    }
+    *reinterpret_cast<float4*>(y + base + (int64_t)p * C) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// (dx may be acc_src: a thread reads its addend before it writes the same float4, and no other thread touches it)
+template <int IPT>
+__global__ __launch_bounds__(kGnSmallThreads) void k_gn_small_bwd(const float* __restrict__ x, const float* __restrict__ dy,
+                                                                  const float* __restrict__ stats, float* __restrict__ sums,
+                                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                  const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                  int ss_stride, const float* acc_src, const float* add2, float* out,
+                                                                  float* out2, int csplit, int P, int C, int act) {
+  __shared__ double red[kGnSmallThreads / 64][2];
+  const int n = blockIdx.x >> 5, grp = blockIdx.x & 31;
+  const int cg = C / 32, q4 = cg / 4, lanes = kGnSmallThreads / q4;
+  const int lane = threadIdx.x / q4, j = threadIdx.x - lane * q4;
+  const int pend = lane < lanes ? P : 0;
+  const int c0 = grp * cg + 4 * j;
+  const int64_t base = (int64_t)n * P * C + c0;
+  const float mean = stats[((int64_t)n * 32 + grp) * 2], rstd = stats[((int64_t)n * 32 + grp) * 2 + 1];
+  float4 xv[IPT], gv[IPT];
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    const int p = lane + k * lanes;
+    const int64_t idx = base + (int64_t)p * C;
+    xv[k] = p < pend ? *reinterpret_cast<const float4*>(x + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+    gv[k] = p < pend ? *reinterpret_cast<const float4*>(dy + idx) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float ga[4], be[4], sc[4], sh[4], A[4], Bc[4], gsc[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int c = c0 + e;
+    ga[e] = gamma[c], be[e] = beta[c];
+    sc[e] = scale != nullptr ? 1.f + scale[(int64_t)n * ss_stride + c] : 1.f;
+    sh[e] = shift != nullptr ? shift[(int64_t)n * ss_stride + c] : 0.f;
+    const float rg = rstd * ga[e];
+    A[e] = rg * sc[e];
+    Bc[e] = (be[e] - mean * rg) * sc[e] + sh[e];
+    gsc[e] = sc[e] * ga[e];
+  }
+  double s0 = 0.0, s1 = 0.0;
+#pragma unroll
+  for (int k = 0; k < IPT; ++k) {
+    if (lane + k * lanes >= pend) continue;
+    const float xs[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+    const float gs[4] = {gv[k].x, gv[k].y, gv[k].z, gv[k].w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float xh = (xs[e] - mean) * rstd;
+      const float t = (xh * ga[e] + be[e]) * sc[e] + sh[e];
+      float g = gs[e];
+      if (act) {
+        const float sg = 1.f / (1.f + __expf(-t));
+        g *= sg * (1.f + t * (1.f - sg));
+      }
+      g *= sc[e] * ga[e];
+      s0 += g;
+      s1 += (double)g * xh;
+    }
+  }
+  gn_small_sum2(s0, s1, red);
+  const double count = (double)P * cg;
+  const float sa = (float)(s0 / count), sb = (float)(s1 / count);
+  if (sums != nullptr && threadIdx.x == 0) sums[((int64_t)n * 32 + grp) * 2] = sa, sums[((int64_t)n * 32 + grp) * 2 + 1] = sb;
+  const bool accumulate = acc_src != nullptr, addend = accumulate || add2 != nullptr;
+  constexpr int KB = IPT < 4 ? IPT : 4;  // items per batch of sweep 2: their addends are in flight together
+#pragma unroll
+  for (int kb = 0; kb < IPT; kb += KB) {
+    float4 ov[KB];
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      const int p = lane + (kb + u) * lanes;
+      const int64_t idx = base + (int64_t)p * C;
+      ov[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (p < pend) {
+        if (accumulate) ov[u] = *reinterpret_cast<const float4*>(acc_src + idx);
+        if (add2 != nullptr) {
+          const float4 t2 = *reinterpret_cast<const float4*>(add2 + idx);
+          if (accumulate)
+            ov[u].x += t2.x, ov[u].y += t2.y, ov[u].z += t2.z, ov[u].w += t2.w;
+          else
+            ov[u] = t2;
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < KB; ++u) {
+      const int k = kb + u;
+      const int p = lane + k * lanes;
+      if (p >= pend) continue;
+      const float xs[4] = {xv[k].x, xv[k].y, xv[k].z, xv[k].w};
+      const float gs[4] = {gv[k].x, gv[k].y, gv[k].z, gv[k].w};
+      const float os[4] = {ov[u].x, ov[u].y, ov[u].z, ov[u].w};
+      float o[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float t = fmaf(xs[e], A[e], Bc[e]);
+        const float xh = (xs[e] - mean) * rstd;
+        float g = gs[e];
+        if (act) {
+          const float sg = 1.f / (1.f + __expf(-t));
+          g *= sg * (1.f + t * (1.f - sg));
+        }
+        g *= gsc[e];
+        o[e] = (addend ? os[e] : 0.f) + rstd * (g - sa - xh * sb);
+      }
+      const int64_t pix = (int64_t)n * P + p;
+      float* dst = out2 == nullptr ? out + pix * C + c0
+                                   : (c0 < csplit ? out + pix * csplit + c0 : out2 + pix * (C - csplit) + (c0 - csplit));
+      *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
+// the kernel instance by float4 items per thread
+template <template <int> class Launch, typename... Args>
+static void gn_small_dispatch(int P, int C, Args... args) {
+  const int lanes = kGnSmallThreads / (C / 128);
+  const int per_thread = (P + lanes - 1) / lanes;
+  if (per_thread <= 1) Launch<1>::go(args...);
+  else if (per_thread <= 2) Launch<2>::go(args...);
+  else if (per_thread <= 4) Launch<4>::go(args...);
+  else if (per_thread <= 8) Launch<8>::go(args...);
+  else Launch<kGnSmallMaxIpt>::go(args...);
+}
+
+template <int IPT>
+struct GnSmallFwd {
+  static void go(hipStream_t st, int N, const float* x, const float* gamma, const float* beta, const float* scale,
+                 const float* shift, int ss_stride, float* y, float* stats, int P, int C, int act) {
+    hipLaunchKernelGGL(k_gn_small_fwd<IPT>, dim3(N * 32), dim3(kGnSmallThreads), 0, st, x, gamma, beta, scale, shift, ss_stride,
+                       y, stats, P, C, act);
+  }
+};
+
+template <int IPT>
+struct GnSmallBwd {
+  static void go(hipStream_t st, int N, const float* x, const float* dy, const float* stats, float* sums, const float* gamma,
+                 const float* beta, const float* scale, const float* shift, int ss_stride, const float* acc_src,
+                 const float* add2, float* dx, float* dx2, int csplit, int P, int C, int act) {
+    hipLaunchKernelGGL(k_gn_small_bwd<IPT>, dim3(N * 32), dim3(kGnSmallThreads), 0, st, x, dy, stats, sums, gamma, beta, scale,
+                       shift, ss_stride, acc_src, add2, dx, dx2, csplit, P, C, act);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
 // Row softmax (rows of length T <= 4096), forward in place and backward  dS = P .* (dP - rowsum(dP .* P))
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_softmax_rows(float* __restrict__ s, int T) {
@@ -2125,6 +2358,39 @@ int fh_groupnorm_bwd_apply_ex(const float* x, const float* dy, const float* stat
     hipLaunchKernelGGL((k_gn_stream<1, false>), dim3(N * nchunks), dim3(256), 0, (hipStream_t)stream, x, dy, stats, sums, gamma,
                        beta, scale, shift, ss_stride, dx, P, C, act, acc_src != nullptr ? 1 : 0, nchunks, kGnChunk, acc_src, add2,
                        dx2, csplit, (unsigned*)nullptr, nt);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- one-launch GroupNorm (k_gn_small_*) ---------------------------------------------------------------------------------
+// 1 where a (P pixels, C channels) tensor takes the one-launch kernels: whole float4s per group and a slice of at most
+// kGnSmallLimit elements.  N is not asked: an image is treated the same whatever batch it arrives in.
+int fh_groupnorm_small_supported(int P, int C) {
+  // FH_GN_SMALL_MAX_PIXELS: the pixel limit for profiles/tools/bench_gn.py, which measures the shapes beyond it as well
+  static const int max_pixels = getenv("FH_GN_SMALL_MAX_PIXELS") ? atoi(getenv("FH_GN_SMALL_MAX_PIXELS")) : kGnSmallMaxPixels;
+  if (P < 1 || P > max_pixels || C < 32 || C % 32 != 0 || (C / 32) % 4 != 0 || C / 128 > kGnSmallThreads) return 0;
+  const int lanes = kGnSmallThreads / (C / 128);  // pixels in flight; a thread holds at most kGnSmallMaxIpt of its quad's
+  return (int64_t)P * (C / 32) <= kGnSmallLimit && (P + lanes - 1) / lanes <= kGnSmallMaxIpt ? 1 : 0;
+}
+
+// y = act(GroupNorm(x) (1 + scale) + shift) and stats [N][32][2] = (mean, rstd) in one launch
+int fh_groupnorm_fwd_small(const float* x, const float* gamma, const float* beta, const float* scale, const float* shift,
+                           int ss_stride, float* y, float* stats, int N, int P, int C, int act, void* stream) {
+  if (!fh_groupnorm_small_supported(P, C) || !x || !gamma || !beta || !y || !stats || N < 1) return FH_EINVAL;
+  gn_small_dispatch<GnSmallFwd>(P, C, (hipStream_t)stream, N, x, gamma, beta, scale, shift, ss_stride, y, stats, P, C, act);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
+// fh_groupnorm_bwd_sums + fh_groupnorm_bwd_apply_ex in one launch (no magnitudes: the half-split mode keeps the three launches);
+// `sums` is an optional OUTPUT here ([N][32][2], null = not wanted): the kernel needs no sums or scratch buffer
+int fh_groupnorm_bwd_small(const float* x, const float* dy, const float* stats, float* sums, const float* gamma,
+                           const float* beta, const float* scale, const float* shift, int ss_stride, const float* acc_src,
+                           const float* add2, float* dx, float* dx2, int csplit, int N, int P, int C, int act, void* stream) {
+  if (!fh_groupnorm_small_supported(P, C) || !x || !dy || !stats || !gamma || !beta || !dx || N < 1) return FH_EINVAL;
+  if (dx2 != nullptr && (csplit <= 0 || csplit >= C || csplit % 4 != 0)) return FH_EINVAL;
+  gn_small_dispatch<GnSmallBwd>(P, C, (hipStream_t)stream, N, x, dy, stats, sums, gamma, beta, scale, shift, ss_stride, acc_src,
+                                add2, dx, dx2, csplit, P, C, act);
   FH_LAUNCH_CHECK();
   return 0;
 }

@@ -327,7 +327,26 @@ class HipOps:
             y.data_ptr(), N, H * W, C, int(act), _lib.stream()), "gn_apply")
         return y
 
+    def _gn_small(self, x):
+        """whether the one-launch GroupNorm kernels take a tensor of x's shape (FH_GN_SMALL=0: the three-launch path)"""
+        N, H, W, C_ = x.shape
+        return os.environ.get("FH_GN_SMALL", "1") != "0" and bool(self.lib.fh_groupnorm_small_supported(H * W, C_))
+
+    def _gn_fwd_small(self, name, x, act, scale=None, shift=None):
+        """statistics and result of a small GroupNorm in one launch (fh_groupnorm_fwd_small) -> (y, stats)"""
+        N, H, W, C_ = x.shape
+        y = torch.empty_like(x)
+        stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
+        ss = 0 if scale is None else scale.stride(0)
+        _lib.check(self.lib.fh_groupnorm_fwd_small(
+            x.data_ptr(), self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(),
+            None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss,
+            y.data_ptr(), stats.data_ptr(), N, H * W, C_, int(act), _lib.stream()), "gn_fwd_small")
+        return y, stats
+
     def _gn(self, name, x, act, scale=None, shift=None):
+        if getattr(x, "_fh_gn", None) is None and self._gn_small(x):
+            return self._gn_fwd_small(name, x, act, scale, shift)
         stats = self._gn_stats(x)
         return self._gn_apply(name, x, stats, act, scale, shift), stats
 
@@ -337,9 +356,13 @@ class HipOps:
         is never written.  Returns (conv output, GroupNorm statistics)."""
         c = self.conv[conv_name]
         N, H, W, Ci = x.shape
+        fuse = (c.wx_f is not None and c.kh == 3 and c.kw == 3 and Ci == c.ci_p and os.environ.get("FH_GN_FUSE", "1") != "0"
+                and self.lib.fh_conv2d_x6_norm_supported(N, H, W, Ci, c.co))
+        if not fuse and getattr(x, "_fh_gn", None) is None and self._gn_small(x):
+            y, stats = self._gn_fwd_small(gn_name, x, act, scale, shift)
+            return self._conv(conv_name, y, res=res), stats
         stats = self._gn_stats(x)
-        if (c.wx_f is not None and c.kh == 3 and c.kw == 3 and Ci == c.ci_p and os.environ.get("FH_GN_FUSE", "1") != "0"
-                and self.lib.fh_conv2d_x6_norm_supported(N, H, W, Ci, c.co)):
+        if fuse:
             table = torch.empty(N, 2, Ci, dtype=torch.float32, device=x.device)
             ss = 0 if scale is None else scale.stride(0)
             _lib.check(self.lib.fh_groupnorm_table(
@@ -367,6 +390,18 @@ class HipOps:
         gp = (self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(),
               None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss)
         sums = getattr(dy, "_fh_gn_sums", None)  # left by the producing input-gradient convolution's epilogue
+        if sums is None and self.bf16 != 4 and self._gn_small(x):  # sums and result in one launch
+            acc = accumulate_into
+            if split is not None:
+                dx = torch.empty(N, H, W, split[0], dtype=torch.float32, device=x.device)
+                dx2 = torch.empty(N, H, W, split[1], dtype=torch.float32, device=x.device)
+            else:
+                dx, dx2 = (acc if acc is not None else torch.empty_like(x)), None
+            _lib.check(self.lib.fh_groupnorm_bwd_small(
+                x.data_ptr(), dy.data_ptr(), stats.data_ptr(), None, *gp, None if acc is None else acc.data_ptr(),
+                None if add2 is None else add2.data_ptr(), dx.data_ptr(), None if dx2 is None else dx2.data_ptr(),
+                0 if split is None else split[0], N, H * W, C_, int(act), _lib.stream()), "gn_bwd_small")
+            return dx if split is None else (dx, dx2)
         if sums is None:
             sums = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
             scratch = torch.empty(self.lib.fh_groupnorm_scratch_doubles(N, H * W), dtype=torch.float64, device=x.device)

@@ -394,6 +394,26 @@ int fh_groupnorm_bwd_apply_ex(const float* x, const float* dy, const float* stat
                               const float* add2, float* dx, float* dx2, int csplit, int N, int P, int C, int act, float* amax2,
                               void* stream);
 
+/* One-launch GroupNorm for small tensors: one workgroup per (image, group) slice keeps the slice on chip between the
+ * statistics sweep and the result sweep, so a GroupNorm costs one launch instead of three (partial, finalize, stream) and a
+ * workgroup touches no memory but its own slice.  fh_groupnorm_small_supported(P, C) == 1 where C % 32 == 0, cg = C / 32 is
+ * a multiple of 4 and the slice of one (image, group), P pixels x cg channels, is within three limits:
+ *   P * cg <= 32768 elements  - what the registers of a 512-thread workgroup hold (16 float4 per thread);
+ *   P <= 1024 pixels          - measured (profiles/gn_small.md): a workgroup pays per cache line, at least one per pixel, and
+ *                               at 4096 pixels the three launches are faster whatever the slice holds;
+ *   P <= 16 * (512 / (cg / 4)) - a thread keeps one channel quad of up to 16 pixels and 512 / (cg / 4) pixels are in flight,
+ *                               rounded down: binds only where cg / 4 does not divide 512 (e.g. C = 1536: 672 pixels).
+ * It does not ask N, so an image is treated the same in every batch.  Elsewhere both entry points return FH_EINVAL.
+ *   fwd: y = act(GroupNorm(x) (1 + scale) + shift) and stats [N][32][2] = (mean, rstd), as fh_groupnorm_stats + _apply;
+ *   bwd: the operands of fh_groupnorm_bwd_apply_ex without amax2 (the half-split mode keeps the three launches); `sums`
+ *        ([N][32][2] = mean g, mean g xhat) is an optional OUTPUT, null = not wanted.  dx may be acc_src (in place). */
+int fh_groupnorm_small_supported(int P, int C);
+int fh_groupnorm_fwd_small(const float* x, const float* gamma, const float* beta, const float* scale, const float* shift,
+                           int ss_stride, float* y, float* stats, int N, int P, int C, int act, void* stream);
+int fh_groupnorm_bwd_small(const float* x, const float* dy, const float* stats, float* sums, const float* gamma,
+                           const float* beta, const float* scale, const float* shift, int ss_stride, const float* acc_src,
+                           const float* add2, float* dx, float* dx2, int csplit, int N, int P, int C, int act, void* stream);
+
 /* 3x3 / stride 1 / pad 1 convolution with a thin output, Cout <= 8 (the 128 -> 6 output convolution and the
  * 128 -> 3 input gradient of the first one): direct form, w [Cout][9][Cin] as for fh_conv2d_nhwc, Cin % 32 == 0. */
 int fh_conv3x3_thin_nhwc(const float* in, const float* w, const float* bias, float* out, int N, int H, int W, int Cin,
