@@ -80,6 +80,8 @@ _SIGS = {
     "fh_conv_circ": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p], C.c_int),
     "fh_conv_circ_plan": ([C.c_int] * 6 + [C.POINTER(C.c_int32)], C.c_int),
+    "fh_conv_window": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_conv_window_plan": ([C.c_int] * 4 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_channel_mix": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_amm": ([C.c_void_p, C.POINTER(FhProblem), c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_dense_matvec_scratch_doubles": ([C.c_int, C.c_int64], C.c_int64),
@@ -258,6 +260,26 @@ class Context:
         assert out.numel() == nimg * (3 if adjoint else 1) * self.S * self.S
         check(self.lib.fh_channel_mix(self.h, ptr(x), ptr(out), ptr(w), nimg, int(adjoint), stream()), "fh_channel_mix")
         return out
+
+    def conv_window(self, x, out, window, planes, adjoint=False):
+        """circular convolution with a dense window = (device tensor [2hy+1][2hx+1], hy, hx), stride 1"""
+        win, hy, hx = window
+        assert win.dtype == torch.float64 and tuple(win.shape) == (2 * hy + 1, 2 * hx + 1)
+        check(self.lib.fh_conv_window(self.h, ptr(x), ptr(out), ptr(win), hy, hx, planes, int(adjoint), stream()),
+              "fh_conv_window")
+        return out
+
+    def blur(self, x, out, taps, planes, stride=1, adjoint=False):
+        """The convolution of a `measurements.Taps` PSF by the route its kind takes: a dense window (fh_conv_window), the two
+        1-D passes of a rank-1 PSF (both at stride 1 only), else the tap list.  x, out: float64 [planes][.][.]."""
+        if taps.window is not None and stride == 1:  # (the decimating operator keeps its tap-list kernels)
+            return self.conv_window(x, out, taps.window, planes, adjoint)
+        if taps.sep is not None and stride == 1:
+            first, second = taps.sep if not adjoint else taps.sep[::-1]
+            tmp = torch.empty_like(out)
+            self.conv(x, tmp, first, planes, 1, adjoint)
+            return self.conv(tmp, out, second, planes, 1, adjoint)
+        return self.conv(x, out, taps, planes, stride, adjoint)
 
     def conv(self, x, out, taps, planes, stride=1, adjoint=False):
         check(self.lib.fh_conv_circ(self.h, ptr(x), ptr(out), ptr(taps.dy), ptr(taps.dx), ptr(taps.w), taps.n,

@@ -63,10 +63,12 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 
 
 # fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
-_OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "super_resolution": 2, "colorization": 3, "noise": 0}
+# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, see _problem)
+_OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
+            "noise": 0}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', or 'noise'.")
+                 "'colorization', 'noise', or 'custom_blur'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -97,6 +99,10 @@ def _problem(operator, cov, sigma_y2):
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
         p.ntaps, p.tap_w = 3, w.data_ptr()
         keep.append(w)
+    elif p.op == 1 and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
+        win, hy, hx = operator.taps.window
+        p.op, p.ntaps, p.halo, p.tap_w = 4, win.numel(), 64 * hy + hx, win.data_ptr()
+        keep.append(win)
     else:
         t = operator.taps
         if t.sep is not None and operator.name != "super_resolution":
@@ -199,6 +205,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
                                                   cov.C.M_dev.data_ptr())
         if name == "colorization":
             assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
+        if name == "custom_blur":
+            assert torch.equal(op.taps.kernel, op0.taps.kernel), "lock-step images must share the PSF"
         if name in _MASKED:
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
@@ -211,15 +219,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
         """op0's blur on the whole batch (planes = 3B)"""
         so = S if (adjoint or prob.stride == 1) else S // prob.stride
         out = torch.empty(B, 3, so, so, dtype=F64, device=dev)
-        t = op0.taps
-        if t.sep is not None and prob.stride == 1:
-            first, second = t.sep if not adjoint else t.sep[::-1]
-            tmp = torch.empty_like(out)
-            ctx.conv(v, tmp, first, planes, 1, adjoint)
-            ctx.conv(tmp, out, second, planes, 1, adjoint)
-        else:
-            ctx.conv(v, out, t, planes, prob.stride, adjoint)
-        return out
+        return ctx.blur(v, out, op0.taps, planes, prob.stride, adjoint)
 
     def mix(v, adjoint):
         """op0's channel mix on the whole batch"""

@@ -46,6 +46,8 @@ SCHEMA = {
     # NEW: the two weight files of LPIPS-VGG (torchvision's vgg16-397923af.pth, lpips' weights/v0.1/vgg.pth); both empty =
     # no LPIPS line in results.txt
     "lpips_vgg_path": (str, ""), "lpips_lin_path": (str, ""),
+    # NEW: the PSF of --operator_name=custom_blur, a 2-D .npy (used as given, not normalised; up to 65 x 65)
+    "kernel_path": (str, ""),
 }
 
 
@@ -71,4 +73,9 @@ def load_config(argv=None):
         raise SystemExit("--outdir=DIR is required")
     if bool(cfg["lpips_vgg_path"]) != bool(cfg["lpips_lin_path"]):
         raise SystemExit("--lpips_vgg_path and --lpips_lin_path go together: LPIPS needs both weight files")
+    if cfg["operator_name"] == "custom_blur" and not cfg["kernel_path"]:
+        raise SystemExit("--operator_name=custom_blur needs --kernel_path=FILE.npy (the PSF, a 2-D array)")
+    if cfg["kernel_path"] and cfg["operator_name"] != "custom_blur":
+        raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur; operator '{cfg['operator_name']}' does not "
+                         "read it")
     return SimpleNamespace(**cfg)

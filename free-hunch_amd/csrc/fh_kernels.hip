@@ -1414,6 +1414,19 @@ struct conv1d_lds {
       : span(k1dAlong + 2 * h), ld(k1dAcross + 1), nblk((2 * h + 1 + k1dTB - 1) / k1dTB), e_off(span * ld),
         bytes(((size_t)e_off + nblk * k1dTB + k1dR) * sizeof(double)) {}
 };
+// k_conv_window: [sx][ld] tile, transposed (a column of the image is contiguous), ld odd | [kh][wp] window, rows zero padded to
+// whole tap blocks.  At hy = hx = 32: 96 x 129 + 65 x 80 doubles = 137.4 KiB (one workgroup per CU; a 31 x 31 window: 54 KiB).
+constexpr int kWinW = 32, kWinH = 64;  // k_conv_window's output tile
+constexpr int kWinR = 8;               //   outputs per thread along a window row
+constexpr int kWinTB = 16;             //   taps per register block
+struct conv_window_lds {
+  int sx, sy, ld, kh, kw, nblk, wp, w_off;
+  size_t bytes;
+  __host__ __device__ constexpr conv_window_lds(int hy, int hx)
+      : sx(kWinW + 2 * hx), sy(kWinH + 2 * hy), ld(sy | 1), kh(2 * hy + 1), kw(2 * hx + 1), nblk((kw + kWinTB - 1) / kWinTB),
+        wp(nblk * kWinTB), w_off((sx * ld + 1) & ~1), bytes(((size_t)w_off + (size_t)kh * wp) * sizeof(double)) {}
+};
+constexpr size_t kLdsWindow = conv_window_lds(32, 32).bytes;  // the opt-in of set_kernel_attributes: the largest window
 
 __global__ __launch_bounds__(256) void k_conv_tile(const double* __restrict__ in, double* __restrict__ out,
                                                    const int* __restrict__ tdy, const int* __restrict__ tdx,
@@ -1547,6 +1560,101 @@ __global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ i
         if (add != nullptr) v = fma(add_scale, add[o], v);
         out[o] = v;
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_conv_window: circular convolution with a DENSE window W[2 hy + 1][2 hx + 1] (a measured PSF, a defocus disk: more
+// non-zeros than a tap list may hold), stride 1.  A dense window needs no offset table: the tap at (a, b) multiplies the
+// input at a fixed distance, so a thread that owns 8 consecutive outputs ALONG a window row reads an input once for up to 8
+// multiply-adds and keeps the 16 weights of a block of taps in registers (k_conv1d's scheme, one window row after another):
+// per 128 multiply-adds 23 conflict-free 8-byte tile reads and 16 broadcast weight reads, where k_conv_tile8 issues 80.
+// Output tile 64 rows x 32 columns: lane = row, wave = 8 columns.  Lanes run ACROSS the window rows' axis, so the tile is
+// staged transposed ([x][y], odd pitch: the 16 lanes of a store group hit 32 different banks).
+// Both directions are one correlation out(py, px) = sum_{a, b} W[a][b] T[py + a][px + b] with a, b ascending from 0 - one fma
+// chain per output in the window's row-major order: the adjoint stages T = in[oy0 - hy + ly][ox0 - hx + lx], the forward
+// operator stages the tile, and stores its outputs, mirrored in both axes (T = in[oy0 + 63 + hy - ly][ox0 + 31 + hx - lx]).
+// Window rows are zero padded to whole blocks of 16 taps (fma(0, v, acc) = acc); reads past the staged columns are 0.
+// ------------------------------------------------------------------------------------------------
+// one block of 16 taps of one window row: e = the block's weights, ca = the first column it reads, 23 columns for 8 outputs.
+// output r multiplies tap t with the column r + t, so column jj feeds the outputs r = jj - t.  GUARD: columns from `ncol` on
+// lie past the staged tile (the zero-padded taps of the row's last block) and read as 0.
+template <bool GUARD>
+__device__ __forceinline__ void window_block(const double* e, const double* ca, int ld, int ncol, double (&acc)[kWinR]) {
+  double wreg[kWinTB];
+#pragma unroll
+  for (int t = 0; t < kWinTB; ++t) wreg[t] = e[t];
+  // all 23 reads are issued before the first multiply-add: with one or two workgroups per CU nothing else hides their latency
+  double v[kWinTB + kWinR - 1];
+#pragma unroll
+  for (int jj = 0; jj < kWinTB + kWinR - 1; ++jj) {
+    v[jj] = ca[(GUARD && jj >= ncol ? ncol - 1 : jj) * ld];  // (ncol >= 8: the load stays inside the tile)
+    if (GUARD && jj >= ncol) v[jj] = 0.0;
+  }
+#pragma unroll
+  for (int jj = 0; jj < kWinTB + kWinR - 1; ++jj) {
+#pragma unroll
+    for (int r = 0; r < kWinR; ++r) {
+      const int t = jj - r;
+      if (t >= 0 && t < kWinTB) acc[r] = fma(wreg[t], v[jj], acc[r]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_conv_window(const double* __restrict__ in, double* __restrict__ out,
+                                                     const double* __restrict__ win, int S, int hy, int hx, int adjoint,
+                                                     const double* __restrict__ add, double add_scale,
+                                                     const fh_cg_state* __restrict__ states) {
+  IMG_GUARD(states, blockIdx.z / 3);
+  extern __shared__ __align__(16) double lds_win[];
+  const conv_window_lds L(hy, hx);
+  const int sx = L.sx, sy = L.sy, ld = L.ld, wp = L.wp;
+  double* tile = lds_win;
+  double* e = lds_win + L.w_off;
+  const int tid = threadIdx.x;
+  const int plane = blockIdx.z;
+  const int oy0 = blockIdx.y * kWinH, ox0 = blockIdx.x * kWinW;
+  const double* src = in + (int64_t)plane * S * S;
+  for (int t = tid; t < L.kh * wp; t += 256) {
+    const int a = t / wp, b = t % wp;
+    e[t] = b < L.kw ? win[a * L.kw + b] : 0.0;
+  }
+  for (int ly = tid >> 6; ly < sy; ly += 4) {  // a wave per tile row: coalesced loads along x, transposed LDS stores
+    int gy = (adjoint ? oy0 - hy + ly : oy0 + kWinH - 1 + hy - ly) % S;
+    gy += gy < 0 ? S : 0;
+    const double* srow = src + (int64_t)gy * S;
+    for (int lx = tid & 63; lx < sx; lx += 64) {
+      int gx = (adjoint ? ox0 - hx + lx : ox0 + kWinW - 1 + hx - lx) % S;
+      gx += gx < 0 ? S : 0;
+      tile[lx * ld + ly] = srow[gx];
+    }
+  }
+  __syncthreads();
+  const int py = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);  // lane = tile row, wave = group of 8 columns
+  double acc[kWinR];
+#pragma unroll
+  for (int r = 0; r < kWinR; ++r) acc[r] = 0.0;
+  const double* col = tile + (g * kWinR) * ld + py;
+  const int ncol = sx - g * kWinR;  // staged columns from this wave's first one on (wave-uniform)
+  for (int a = 0; a < L.kh; ++a) {
+    const double* ea = e + a * wp;
+    const double* ca = col + a;
+    // every block but the last of a window row ends inside the staged columns (16 tb + 22 < 16 nblk - 8 <= ncol)
+    for (int tb = 0; tb + 1 < L.nblk; ++tb) window_block<false>(ea + tb * kWinTB, ca + tb * kWinTB * ld, ld, 0, acc);
+    window_block<true>(ea + (L.nblk - 1) * kWinTB, ca + (L.nblk - 1) * kWinTB * ld, ld, ncol - (L.nblk - 1) * kWinTB, acc);
+  }
+  const int oy = adjoint ? oy0 + py : oy0 + kWinH - 1 - py;
+  if (oy >= S) return;
+#pragma unroll
+  for (int r = 0; r < kWinR; ++r) {
+    const int px = g * kWinR + r;
+    const int ox = adjoint ? ox0 + px : ox0 + kWinW - 1 - px;
+    if (ox < S) {
+      const int64_t o = (int64_t)plane * S * S + (int64_t)oy * S + ox;
+      double v = acc[r];
+      if (add != nullptr) v = fma(add_scale, add[o], v);
+      out[o] = v;
     }
   }
 }
@@ -2099,8 +2207,43 @@ static int conv_launch(fh_context* ctx, const double* in, double* out, const int
   return 0;
 }
 
+// The launch plan of fh_conv_window (fh_conv_window_plan reports it): one kernel, its grid and its LDS from conv_window_lds.
+static int window_plan(int S, int hy, int hx, int planes, dim3* grid, size_t* lds) {
+  if (S < 2 || S > 256 || (S & 1) || hy < 0 || hy > 32 || hx < 0 || hx > 32 || planes < 1) return FH_EINVAL;
+  *lds = conv_window_lds(hy, hx).bytes;
+  if (*lds > kLdsWindow || planes > 65535) return FH_ESIZE;  // (the plane is grid dimension z)
+  *grid = dim3((unsigned)((S + kWinW - 1) / kWinW), (unsigned)((S + kWinH - 1) / kWinH), (unsigned)planes);
+  return 0;
+}
+
+static int window_launch(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes,
+                         int adjoint, const double* add, double add_scale, const fh_cg_state* done, hipStream_t st) {
+  dim3 grid;
+  size_t lds;
+  const int rc = window_plan(ctx->S, hy, hx, planes, &grid, &lds);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_conv_window, grid, dim3(256), lds, st, in, out, win, ctx->S, hy, hx, adjoint, add, add_scale, done);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
+// fh_problem.op = 4 (dense-window blur): tap_w is the window, halo = 64 hy + hx, and nothing of the tap-list operators is set
+static int window_problem_check(const fh_problem* p) {
+  const int hy = p->halo / 64, hx = p->halo % 64;
+  if (p->halo < 0 || hy > 32 || hx > 32 || p->ntaps != (2 * hy + 1) * (2 * hx + 1) || p->stride != 1) return FH_EINVAL;
+  if (p->tap_w == nullptr || p->tap_dy || p->tap_dx || p->ntaps2 != 0 || p->tap2_dy || p->tap2_dx || p->tap2_w) return FH_EINVAL;
+  if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
+  return 0;
+}
+
+// what fh_amm / fh_cg_solve[_batched] refuse before anything is launched
+static int problem_check(const fh_problem* p) {
+  if (p->op < 0 || p->op > 4) return FH_EINVAL;
+  return p->op == 4 ? window_problem_check(p) : 0;
+}
+
 // ------------------------------------------------------------------------------------------------
-// A_mm(u) = sigma_y^2 u + A C A^T u       (conditioning_mechanisms.py:395-400, 505-511, 653-659)
+// A_mm(u) = sigma_y^2 u + A C A^T u      (conditioning_mechanisms.py:395-400, 505-511, 653-659)
 // ------------------------------------------------------------------------------------------------
 // dot_part / dot_nparts (CG only): where the operator's last pass can also reduce u . (A u) per image it writes *dot_nparts
 // block partials per image to dot_part (stride kCgScratch) - the caller then skips its own dot kernel; else *dot_nparts = 0
@@ -2139,8 +2282,8 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   const int nimg = per.nimg;
   const int planes = p->planes * nimg;
   if (d != (int64_t)p->planes * S * S || p->planes != 3 || nimg < 1 || nimg > ctx->nimg_max) return FH_EINVAL;
-  if (p->op < 0 || p->op > 3) return FH_EINVAL;
-  int rc;
+  int rc = problem_check(p);
+  if (rc) return rc;
   double *w0 = ctx->w0, *w1 = ctx->w1;
   if (p->op == 3) {
     // colorization: u, out are ONE plane per image, A = channel mix with the three weights in tap_w.  The 2-D DCT acts per
@@ -2215,6 +2358,9 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   // w0 = A^T u
   if (p->op == 0) {
     hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, u, (const double*)nullptr, 0.0, w0, d, states);
+  } else if (p->op == 4) {
+    rc = window_launch(ctx, u, w0, p->tap_w, halo / 64, halo % 64, planes, 1, nullptr, 0.0, states, st);
+    if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, u, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
                      states, st);
@@ -2248,6 +2394,9 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   // out = sigma_y^2 u + A w1
   if (p->op == 0) {
     hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out, d, states);
+  } else if (p->op == 4) {
+    rc = window_launch(ctx, w1, out, p->tap_w, halo / 64, halo % 64, planes, 0, u, p->sigma_y2, states, st);
+    if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
     if (rc) return rc;
@@ -2428,6 +2577,7 @@ static int set_kernel_attributes() {
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
   for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
+  FH_CHECK(hipFuncSetAttribute((const void*)k_conv_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
   return 0;
 }
 
@@ -2969,6 +3119,24 @@ int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int ad
   return 0;
 }
 
+int fh_conv_window(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes, int adjoint,
+                   void* stream) {
+  if (!ctx || !in || !out || !win || in == out) return FH_EINVAL;
+  return window_launch(ctx, in, out, win, hy, hx, planes, adjoint, nullptr, 0.0, nullptr, (hipStream_t)stream);
+}
+
+int fh_conv_window_plan(int S, int hy, int hx, int planes, int32_t out[5]) {
+  if (out == nullptr) return FH_EINVAL;
+  for (int i = 0; i < 5; ++i) out[i] = 0;
+  dim3 grid;
+  size_t lds;
+  const int rc = window_plan(S, hy, hx, planes, &grid, &lds);
+  if (rc) return rc;
+  const int32_t v[5] = {(int32_t)grid.x, (int32_t)grid.y, (int32_t)grid.z, 256, (int32_t)lds};
+  memcpy(out, v, sizeof(v));
+  return 0;
+}
+
 int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double* w, int nimg, int adjoint, void* stream) {
   if (!ctx || !in || !out || !w || nimg < 1 || (ctx->S & 1)) return FH_EINVAL;
   if (((uintptr_t)in | (uintptr_t)out) & 15) return FH_EINVAL;  // 16-byte accesses
@@ -2987,7 +3155,7 @@ int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double*
 
 int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, void* stream) {
   if (!ctx || !p || !u || !out) return FH_EINVAL;
-  if (p->op < 0 || p->op > 3) return FH_EINVAL;
+  if (problem_check(p)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)u | (uintptr_t)out) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const fh_batch per = batch_of(p);
   const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
@@ -3085,7 +3253,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (nimg < 1 || nimg > ctx->nimg_max || nimg > FH_MAX_BATCH) return FH_ESIZE;
   hipStream_t st = (hipStream_t)stream;
   const int S = ctx->S;
-  if (p->op < 0 || p->op > 3 || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
+  if (problem_check(p) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const int So = S / (p->op == 2 ? p->stride : 1);
   const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)

@@ -47,6 +47,7 @@ class _TapList:
         cy, cx = k.shape[0] // 2, k.shape[1] // 2
         self.n = int(ys.size)
         hy, hx = int(np.abs(ys - cy).max()), int(np.abs(xs - cx).max())
+        self.hy, self.hx = hy, hx
         # fh_conv_circ halo code: for 1-D lists -(h+1) (column kernel, dx = 0) / -(h+101) (row kernel), else both extents
         # (1000 + 64 hy + hx), so that the kernel stages only the halo the taps reach
         self.halo = -(hy + 1) if (hx == 0 and hy > 0) else (-(hx + 101) if (hy == 0 and hx > 0) else 1000 + 64 * hy + hx)
@@ -60,7 +61,14 @@ class Taps(_TapList):
     A numerically rank-1 PSF (the shipped Gaussian: second singular value 1e-8 of the first once rounded to float32,
     1e-16 before) is additionally split into a column and a row tap list (`sep`), so that the blur runs as two 1-D
     passes: 2 x 25 instead of 625 taps per pixel.  The rank-1 factor differs from the float32 taps by < 1e-7
-    relative, the same size as the float32 rounding of the PSF / the complex64 OTF the reference blurs with."""
+    relative, the same size as the float32 rounding of the PSF / the complex64 OTF the reference blurs with.
+    A PSF that is not rank-1 and has more non-zeros than a tap list may hold (MAX_TAPS; a measured PSF, a defocus disk)
+    additionally gets `window` = (device tensor [2hy+1][2hx+1], hy, hx): the PSF about its centre, zero padded to odd sides
+    (fh_conv_window).  So does a PSF that fills at least half of its window: the window kernel's time goes with the window's
+    area, rows padded to whole blocks of 16 taps, the tap-list kernel's with the number of taps, and per multiply-add the
+    window kernel measured 2.25x faster (a full 31 x 31 window at 256 x 256: 91.5 us against 205.8 us,
+    profiles/custom_psf.md) - half is that ratio with a margin.  The shipped motion PSF fills 11 % of its window."""
+    MAX_TAPS = 1024  # kMaxTaps of csrc/fh_kernels.hip
 
     def __init__(self, kernel, device):
         k = np.asarray(kernel, dtype=np.float32).astype(np.float64)  # the reference holds the PSF in float32
@@ -76,6 +84,21 @@ class Taps(_TapList):
                 col[np.abs(col) < 1e-12 * np.abs(col).max()] = 0.0
                 row[np.abs(row) < 1e-12 * np.abs(row).max()] = 0.0
                 self.sep = (_TapList(col[:, None], device), _TapList(row[None, :], device))
+        self.window = None
+        area = (2 * self.hy + 1) * (-(-(2 * self.hx + 1) // 16) * 16)  # what k_conv_window multiplies per output
+        if self.sep is None and min(k.shape) > 1 and (self.n > self.MAX_TAPS or 2 * self.n >= area or not self._tap_list_fits()):
+            ys, xs = np.nonzero(k)
+            win = np.zeros((2 * self.hy + 1, 2 * self.hx + 1))
+            win[ys - k.shape[0] // 2 + self.hy, xs - k.shape[1] // 2 + self.hx] = k[ys, xs]
+            self.window = (torch.from_numpy(win).to(device), self.hy, self.hx)
+
+    def _tap_list_fits(self):
+        """False where fh_conv_circ has no stride-1 launch for this list (wide extents with several hundred taps overflow the
+        tile kernels' LDS: FH_ESIZE); asked of the library's own plan, which needs no device."""
+        import ctypes
+        plan = _lib.load().fh_conv_circ_plan
+        out = (ctypes.c_int32 * 6)()
+        return all(plan(256, self.n, self.halo, 3, 1, adjoint, out) == 0 for adjoint in (0, 1))
 
 
 def dct_basis_longdouble(S):
@@ -146,14 +169,7 @@ class LinearOperator:
         so = S if (adjoint or stride == 1) else S // stride
         out = torch.empty(x64.shape[0], x64.shape[1], so, so, dtype=F64, device=self.device)
         planes = x64.shape[0] * x64.shape[1]
-        if self.taps.sep is not None and stride == 1:
-            first, second = self.taps.sep if not adjoint else self.taps.sep[::-1]
-            tmp = torch.empty_like(out)
-            self._ctx().conv(x64, tmp, first, planes, 1, adjoint)
-            self._ctx().conv(tmp, out, second, planes, 1, adjoint)
-        else:
-            self._ctx().conv(x64, out, self.taps, planes, stride, adjoint)
-        return out
+        return self._ctx().blur(x64, out, self.taps, planes, stride, adjoint)
 
     def folded_bases(self):
         """(device copies of `folded_dct_blur_bases` for this operator's separable PSF, packed-symmetric flag) - None when
@@ -228,7 +244,7 @@ class _BlurOperator(LinearOperator):
         return self._conv(v, adjoint=True).to(v.dtype)
 
     def get_kernel(self):
-        return self.taps.kernel.view(1, 1, self.kernel_size, self.kernel_size).to(self.device)
+        return self.taps.kernel.view(1, 1, *self.taps.kernel.shape).to(self.device)
 
 
 @register_operator(name="gaussian_blur")
@@ -239,6 +255,37 @@ class GaussialBlurOperator(_BlurOperator):  # (sic) the reference's class name, 
 @register_operator(name="motion_blur")
 class MotionBlurOperator(_BlurOperator):  # measurements.py:126 (weights come from the shipped .npy, :135-136)
     kernel_file = "motion_ks61_std0.5.npy"
+
+
+@register_operator(name="custom_blur")
+class CustomBlurOperator(_BlurOperator):
+    """Circular blur with the caller's own PSF: `kernel_path` (a 2-D .npy) or `kernel` (a 2-D array), rounded to float32 like
+    the shipped PSFs and used AS GIVEN - not normalised, centre at index size // 2 in both axes.  A rank-1 PSF runs as two
+    1-D passes (and folds into the DCT passes), a sparse one on the tap-list kernels, a dense one on fh_conv_window
+    (`Taps`).  The extent about the centre is at most 32 in either axis (PSFs up to 65 x 65)."""
+
+    def __init__(self, in_shape, sigma_s, device, kernel_path=None, kernel=None, **kwargs):
+        if (kernel_path is None or kernel_path == "") == (kernel is None):
+            raise ValueError("custom_blur needs exactly one of kernel_path (a 2-D .npy file) and kernel (a 2-D array)")
+        k = np.load(kernel_path) if kernel is None else np.asarray(kernel)
+        if k.ndim != 2 or k.size == 0:
+            raise ValueError(f"custom_blur: the PSF must be a 2-D array, got shape {tuple(k.shape)}")
+        k = np.asarray(k, dtype=np.float32)
+        if not np.isfinite(k).all():
+            raise ValueError("custom_blur: the PSF has a non-finite entry (also after rounding to float32)")
+        if not k.any():
+            raise ValueError("custom_blur: the PSF is all zero")
+        ys, xs = np.nonzero(k)
+        hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
+        if max(hy, hx) > 32:
+            raise ValueError(f"custom_blur: the PSF reaches ({hy}, {hx}) samples from its centre at index size // 2; the "
+                             "kernels stage at most 32 (PSFs up to 65 x 65)")
+        self.device = torch.device(device)
+        self.kernel_size = tuple(k.shape)  # (rows, columns)
+        self.kernel = k
+        self.taps = Taps(k, self.device)
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
 
 
 def _cubic(x):

@@ -190,6 +190,19 @@ int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* 
  * 1 k_conv1d<1>, 2 k_conv_tile8, 3 k_conv_tile, 4 k_conv_dec, 5 k_conv_up, 6 k_conv_direct. */
 int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int adjoint, int32_t out[6]);
 
+/* Circular 2-D convolution with a DENSE window win[2 hy + 1][2 hx + 1] (row-major, centre at (hy, hx), 0 <= hy, hx <= 32; zeros
+ * inside the window are allowed) over in[planes][S][S] at stride 1 - fh_conv_circ's definition with dy = a, dx = b and no
+ * limit on the number of non-zeros (a measured PSF, a defocus disk, a rotated Gaussian):
+ *   adjoint = 0:  out[p][i][j] = sum_{a=-hy..hy} sum_{b=-hx..hx} win[a+hy][b+hx] * in[p][(i-a) mod S][(j-b) mod S]
+ *   adjoint = 1:  out[p][i][j] = sum_{a,b}                        win[a+hy][b+hx] * in[p][(i+a) mod S][(j+b) mod S]
+ * One fma chain per output in the window's row-major order: an output does not depend on planes or on the launch.
+ * FH_EINVAL: a null pointer, hy or hx outside 0..32, planes < 1, in == out; FH_ESIZE: no launch fits (planes > 65535).
+ * fh_conv_window_plan reports the launch for a context of image side S without a context or a device:
+ * out = {grid x, grid y, grid z, block size, dynamic LDS bytes} (zeros on an error). */
+int fh_conv_window(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes, int adjoint,
+                   void* stream);
+int fh_conv_window_plan(int S, int hy, int hx, int planes, int32_t out[5]);
+
 /* Channel mix of the colorization operator, measurement_utils/measurements.py:74-84 (A = mean over the colour channels,
  * here with three weights w[0..2] on the device; (1/3, 1/3, 1/3) is the reference's operator):
  *   adjoint = 0:  in [nimg][3][S][S] -> out [nimg][S][S],     out = sum_c w[c] * in_c
@@ -204,6 +217,8 @@ typedef struct fh_problem {
    * d = 3 S S as for the others, but the measurement - u, b, x of fh_amm / fh_cg_solve[_batched] - is ONE plane per image,
    * n = S S.  The 2-D DCT acts per plane, so with use_dct = 1  A C A^T u = idct2(sum_c w_c (C_dct (w_c dct2(u)))_c): one
    * forward and one inverse DCT over one plane per image, and with m = 0 it is idct2(D_eff .* dct2(u)), D_eff = sum_c w_c^2 D_c.
+   * 4 dense-window blur: A = fh_conv_window with the window in tap_w, halo = 64 * hy + hx, ntaps = (2 hy + 1)(2 hx + 1),
+   * stride = 1; tap_dy, tap_dx, tap2_* and fold_* null and ntaps2 = 0 (anything else: FH_EINVAL before any launch).
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
