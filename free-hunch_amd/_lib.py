@@ -56,6 +56,7 @@ _SIGS = {
     "fh_context_status": ([C.c_void_p, C.c_void_p], C.c_int),
     "fh_debug_read_stamps": ([C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p], C.c_int),
     "fh_dct2d": ([C.c_void_p, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_dct_sym_plan": ([C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_int64)], C.c_int),
     "fh_dct_moments_u8": ([C.c_void_p, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_rep_apply": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
     "fh_rep_apply_batched": ([C.c_void_p, C.POINTER(FhBatch), C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),

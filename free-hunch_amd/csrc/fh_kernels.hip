@@ -195,29 +195,39 @@ struct fh_diag_tab {
   const double* D[FH_MAX_BATCH];  // null table (D[0] == nullptr): no scaling
 };
 
-template <bool INV, int PPI = 3>  // PPI: planes per image (3, or 1 for the colorization operator's measurement plane)
-__global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, const double* __restrict__ X,
-                                                 double* __restrict__ C, int S, int planes,
-                                                 const fh_cg_state* __restrict__ states, const double* __restrict__ add,
-                                                 double add_scale, fh_diag_tab dg, double* __restrict__ dot_part,
-                                                 int dot_stride) {
+// NS: plane streams per workgroup.  NS = 2 is a 512-thread workgroup whose two 4-wave halves share the resident half-basis
+// slices and each walk a plane list of their own with their own staging buffers and accumulators: two waves per SIMD, so
+// one half's MFMAs run under the other half's load waits, and 12 planes at S = 256 are one task per half on 192 workgroups
+// instead of two tasks back to back on half of 256 (profiles/dct_streams.md).  tid = threadIdx.x & 255 drives the same
+// staging map, wave tile and epilogue in either half; every output keeps its chain of MFMA accumulations (k ascending in
+// steps of 4, parities apart), so the result does not depend on NS.
+template <bool INV, int PPI = 3, int NS = 1>  // PPI: planes per image (3, or 1 for the colorization operator's measurement plane)
+__global__ __launch_bounds__(256 * NS) void k_dct_sym(const double* __restrict__ Ah, const double* __restrict__ X,
+                                                      double* __restrict__ C, int S, int planes,
+                                                      const fh_cg_state* __restrict__ states, const double* __restrict__ add,
+                                                      double add_scale, fh_diag_tab dg, double* __restrict__ dot_part,
+                                                      int dot_stride) {
   // dot_part != null (with add): the workgroup also leaves sum(add .* out) of every (plane, tile) it completes in
   // dot_part[image * dot_stride + (plane % PPI) * tiles + tile] - the p.Ap reduction of the CG iteration rides in the pass
   // that produces Ap (A p = sigma_y^2 p + ..., add = p), summed later in a fixed order
-  // K chunks of 64 (two per plane at S = 256): the per-chunk cost besides the 16 MFMA pairs - LDS stores, the barrier, the
-  // wait for the prefetched rows - was ~65 % of a 32-wide chunk's time (measured 14.4 us per pass at BK = 32, 36 % of the f64
-  // MFMA rate); halving the chunk count halves it.  Two LDS buffers, the next chunk prefetched into registers.
-  constexpr int TJ = 32, TR = 32, BK = 64, LDB = BK + 2, NBUF = 2, NP8 = BK / 32;  // NP8 pieces of 8 doubles per thread
+  // NS = 1: K chunks of 64 (two per plane at S = 256): the per-chunk cost besides the 16 MFMA pairs - LDS stores, the
+  // barrier, the wait for the prefetched rows - was ~65 % of a 32-wide chunk's time (measured 14.4 us per pass at BK = 32,
+  // 36 % of the f64 MFMA rate); halving the chunk count halves it.  Two LDS buffers, the next chunk prefetched into registers.
+  // NS = 2: two streams of double buffers do not fit beside the basis (201 728 B).  One 64-wide buffer per stream does
+  // (134 144 B) at the price of a second barrier per chunk, and measured faster than double-buffered chunks of 32
+  // (136 192 B): 22.0 against 23.1 us for the two passes over 12 planes (profiles/dct_streams.md).
+  constexpr int TJ = 32, TR = 32, BK = 64, LDB = BK + 2, NBUF = NS == 2 ? 1 : 2, NP8 = BK / 32;  // NP8 pieces of 8 doubles per thread
   extern __shared__ __align__(16) double smem[];
   const int H = S >> 1, LDA = H + 2;
-  double* As_e = smem;                      // [TJ][LDA] resident half-basis slices
+  const int half = NS == 2 ? (int)(threadIdx.x >> 8) : 0;
+  double* As_e = smem;                      // [TJ][LDA] resident half-basis slices (shared by the halves)
   double* As_o = As_e + TJ * LDA;           // [TJ][LDA]
-  double* Bs = As_o + TJ * LDA;             // [NBUF buffers][2 parities][TR][LDB]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double* Bs = As_o + TJ * LDA + half * (NBUF * 2 * TR * LDB);  // per half: [NBUF buffers][2 parities][TR][LDB]
+  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;  // wave: within the half
   const int li = lane & 15, lk = lane >> 4;
   const int jw = (wave >> 1) * 16, rw = (wave & 1) * 16;
   const int j0 = blockIdx.y * TJ, r0 = blockIdx.x * TR;
-  for (int i = tid; i < TJ * (H / 2); i += 256) {
+  for (int i = threadIdx.x; i < TJ * (H / 2); i += 256 * NS) {
     const int row = i / (H / 2), c2 = (i % (H / 2)) * 2;
     const double2 ve = *reinterpret_cast<const double2*>(Ah + (int64_t)(j0 + row) * H + c2);
     const double2 vo = *reinterpret_cast<const double2*>(Ah + (int64_t)H * H + (int64_t)(j0 + row) * H + c2);
@@ -226,12 +236,20 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
   }
   const int srow = tid >> 3, sq = tid & 7;  // staging: row of the r tile, lane within the row's 8-thread group
   const int nkc = H / BK;
-  // planes of this workgroup: p = blockIdx.z, + gridDim.z, ...  (finished images of a CG batch are skipped)
-  int pl[8], npl = 0;
-  for (int p = blockIdx.z; p < planes && npl < 8; p += gridDim.z)
+  // planes of this half's stream s: p = s, s + streams, ...  (finished images of a CG batch are skipped).  Both halves
+  // take every barrier, so the loop runs the longer half's trip count: each thread counts the other half's planes too.
+  const int nstreams = (int)gridDim.z * NS;
+  int pl[8], npl = 0, npl_other = 0;
+  // Half h of workgroup z is stream h * gridDim.z + z: where the streams are uneven (24 planes on 16 streams) every
+  // workgroup pairs a long stream with a short one; pairing neighbours (2 z + h) left half the workgroups with two long
+  // streams and measured 37.5 against 34.2 us for the two passes over 24 planes (profiles/dct_streams.md).
+  for (int p = half * (int)gridDim.z + (int)blockIdx.z; p < planes && npl < 8; p += nstreams)
     if (states == nullptr || states[p / PPI].done == 0) pl[npl++] = p;
-  const int total = npl * nkc;
-  if (total == 0) return;
+  if (NS == 2)
+    for (int p = (1 - half) * (int)gridDim.z + (int)blockIdx.z; p < planes && npl_other < 8; p += nstreams)
+      if (states == nullptr || states[p / PPI].done == 0) ++npl_other;
+  const int total = npl * nkc, trips = (npl > npl_other ? npl : npl_other) * nkc;
+  if (trips == 0) return;  // (uniform over the workgroup)
   double ra[NP8][8];
   auto load_chunk = [&](int t) {
     const double* row = X + (int64_t)pl[t / nkc] * S * S + (int64_t)(r0 + srow) * S;
@@ -273,63 +291,75 @@ __global__ __launch_bounds__(256) void k_dct_sym(const double* __restrict__ Ah, 
       }
     }
   };
-  load_chunk(0);
-  store_chunk(0);
+  if (NS == 1 || total > 0) {
+    load_chunk(0);
+    store_chunk(0);
+  }
   __syncthreads();
   double4_t acc_e = {0.0, 0.0, 0.0, 0.0}, acc_o = {0.0, 0.0, 0.0, 0.0};
   int buf = 0;
-  for (int t = 0; t < total; ++t, buf ^= 1) {
-    const bool more = t + 1 < total;
+  for (int t = 0; t < trips; ++t, buf ^= NBUF - 1) {
+    // a half past its own plane list does no loads, MFMAs or stores and only arrives at the barriers
+    const bool active = NS == 1 || t < total, more = t + 1 < total;
     if (more) load_chunk(t + 1);
     const int kc = t % nkc;
-    const double* be = Bs + (buf * 2 + 0) * TR * LDB + (rw + li) * LDB + lk;
-    const double* bo = Bs + (buf * 2 + 1) * TR * LDB + (rw + li) * LDB + lk;
-    const double* ae = As_e + (jw + li) * LDA + kc * BK + lk;
-    const double* ao = As_o + (jw + li) * LDA + kc * BK + lk;
+    if (active) {
+      const double* be = Bs + (buf * 2 + 0) * TR * LDB + (rw + li) * LDB + lk;
+      const double* bo = Bs + (buf * 2 + 1) * TR * LDB + (rw + li) * LDB + lk;
+      const double* ae = As_e + (jw + li) * LDA + kc * BK + lk;
+      const double* ao = As_o + (jw + li) * LDA + kc * BK + lk;
 #pragma unroll
-    for (int kk = 0; kk < BK; kk += 4) {
-      acc_e = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[kk], be[kk], acc_e, 0, 0, 0);
-      acc_o = __builtin_amdgcn_mfma_f64_16x16x4f64(ao[kk], bo[kk], acc_o, 0, 0, 0);
+      for (int kk = 0; kk < BK; kk += 4) {
+        acc_e = __builtin_amdgcn_mfma_f64_16x16x4f64(ae[kk], be[kk], acc_e, 0, 0, 0);
+        acc_o = __builtin_amdgcn_mfma_f64_16x16x4f64(ao[kk], bo[kk], acc_o, 0, 0, 0);
+      }
     }
-    if (kc == nkc - 1) {  // a plane is complete: write its two output row families
-      const int plane = pl[t / nkc];
-      double* Cp = C + (int64_t)plane * S * S;
-      const double* Ap = add != nullptr ? add + (int64_t)plane * S * S : nullptr;
-      const double* Dp = dg.D[0] != nullptr ? dg.D[plane / PPI] + (int64_t)(plane % PPI) * S * S : nullptr;
-      const int col = r0 + rw + li;
+    if (kc == nkc - 1) {  // the active halves complete a plane (kc is uniform): write its two output row families
+      const int plane = active ? pl[t / nkc] : 0;
       double dsum = 0.0;
+      if (active) {
+        double* Cp = C + (int64_t)plane * S * S;
+        const double* Ap = add != nullptr ? add + (int64_t)plane * S * S : nullptr;
+        const double* Dp = dg.D[0] != nullptr ? dg.D[plane / PPI] + (int64_t)(plane % PPI) * S * S : nullptr;
+        const int col = r0 + rw + li;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int jj = j0 + jw + lk + 4 * q;
-        int64_t o0, o1;
-        double v0, v1;
-        if (INV) {
-          o0 = (int64_t)jj * S + col, o1 = (int64_t)(S - 1 - jj) * S + col;
-          v0 = acc_e[q] + acc_o[q], v1 = acc_e[q] - acc_o[q];
-        } else {
-          o0 = (int64_t)(2 * jj) * S + col, o1 = o0 + S;
-          v0 = acc_e[q], v1 = acc_o[q];
+        for (int q = 0; q < 4; ++q) {
+          const int jj = j0 + jw + lk + 4 * q;
+          int64_t o0, o1;
+          double v0, v1;
+          if (INV) {
+            o0 = (int64_t)jj * S + col, o1 = (int64_t)(S - 1 - jj) * S + col;
+            v0 = acc_e[q] + acc_o[q], v1 = acc_e[q] - acc_o[q];
+          } else {
+            o0 = (int64_t)(2 * jj) * S + col, o1 = o0 + S;
+            v0 = acc_e[q], v1 = acc_o[q];
+          }
+          if (Dp != nullptr) v0 = Dp[o0] * v0, v1 = Dp[o1] * v1;  // same product as k_rep_apply2 forms for m = 0
+          if (Ap != nullptr) {
+            const double a0 = Ap[o0], a1 = Ap[o1];
+            v0 = fma(add_scale, a0, v0), v1 = fma(add_scale, a1, v1);
+            dsum = fma(a0, v0, fma(a1, v1, dsum));
+          }
+          Cp[o0] = v0;
+          Cp[o1] = v1;
         }
-        if (Dp != nullptr) v0 = Dp[o0] * v0, v1 = Dp[o1] * v1;  // same product as k_rep_apply2 forms for m = 0
-        if (Ap != nullptr) {
-          const double a0 = Ap[o0], a1 = Ap[o1];
-          v0 = fma(add_scale, a0, v0), v1 = fma(add_scale, a1, v1);
-          dsum = fma(a0, v0, fma(a1, v1, dsum));
-        }
-        Cp[o0] = v0;
-        Cp[o1] = v1;
+        acc_e = double4_t{0.0, 0.0, 0.0, 0.0};
+        acc_o = double4_t{0.0, 0.0, 0.0, 0.0};
       }
-      if (dot_part != nullptr) {  // (uniform: every thread of the workgroup completes the plane in this iteration)
-        __shared__ double dred[4];
-        dsum = block_sum_256(dsum, dred);
-        if (tid == 0)
+      if (dot_part != nullptr) {  // (uniform: every thread takes these barriers on every plane-completing trip)
+        // block_sum_256 per half: each half sums its own four wave partials, in the same order, from its own four slots
+        __shared__ double dred[4 * NS];
+        dsum = wave_sum(dsum);
+        __syncthreads();
+        if (lane == 0) dred[4 * half + wave] = dsum;
+        __syncthreads();
+        if (active && tid == 0)
           dot_part[(int64_t)(plane / PPI) * dot_stride + (plane % PPI) * (int)(gridDim.x * gridDim.y) + blockIdx.y * gridDim.x +
-                   blockIdx.x] = dsum;
+                   blockIdx.x] = dred[4 * half] + dred[4 * half + 1] + dred[4 * half + 2] + dred[4 * half + 3];
       }
-      acc_e = double4_t{0.0, 0.0, 0.0, 0.0};
-      acc_o = double4_t{0.0, 0.0, 0.0, 0.0};
     }
-    if (more) store_chunk(buf ^ 1);
+    if (NBUF == 1) __syncthreads();  // every wave is done reading the one buffer
+    if (more) store_chunk(buf ^ (NBUF - 1));
     __syncthreads();
   }
 }
@@ -412,17 +442,43 @@ static bool sym_dct(const fh_context* ctx) {
   return ctx->sym_fwd != nullptr && !no_sym;
 }
 
+// Launch plan of a symmetric pass over `planes` planes of side S (host arithmetic only).  One (plane, 32 x 32 tile) task
+// is a fixed amount of work and a workgroup owns a CU (its LDS), so with more tasks than the 256 CUs a workgroup would run
+// tasks back to back: then it runs two plane streams side by side (ns = 2, k_dct_sym<.., 2>), gz = ceil(planes / 2) capped
+// at 256 workgroups.  Otherwise one stream per workgroup, the z extent filling the CUs.  A stream holds at most 8 planes.
+// FH_DCT_STREAMS=1 keeps one stream per workgroup at every size (A/B switch, read once per process).
+struct dct_sym_plan_t {
+  int gx, gy, gz, ns;
+  int64_t lds_bytes;
+};
+static dct_sym_plan_t dct_sym_plan(int S, int planes) {
+  static const bool one_stream = getenv("FH_DCT_STREAMS") != nullptr && atoi(getenv("FH_DCT_STREAMS")) == 1;
+  const int H = S / 2;
+  dct_sym_plan_t pn;
+  pn.gx = S / 32, pn.gy = H / 32;
+  const int tiles = pn.gx * pn.gy, cap = 256 / tiles;
+  pn.ns = (int64_t)planes * tiles > 256 && !one_stream ? 2 : 1;
+  pn.gz = pn.ns == 2 ? ((planes + 1) / 2 < cap ? (planes + 1) / 2 : cap) : cap;
+  const int need = (planes + 8 * pn.ns - 1) / (8 * pn.ns);  // streams of at most 8 planes
+  if (pn.gz < need) pn.gz = need;
+  if (pn.ns == 1 && pn.gz > planes) pn.gz = planes;
+  if (pn.gz < 1) pn.gz = 1;
+  // doubles: the resident slices, then [2 parities][32][66] staging buffers - two of one stream, or one of each of two
+  pn.lds_bytes = ((int64_t)2 * 32 * (H + 2) + (int64_t)2 * 2 * 32 * 66) * (int64_t)sizeof(double);
+  return pn;
+}
+
 // the two launches of a symmetric 2-D pass: along W into the context's intermediate, then along H with the epilogue operands
-template <bool INV, int PPI>
+template <bool INV, int PPI, int NS>
 static void dct_sym_pair(fh_context* ctx, dim3 grid, size_t lds, hipStream_t st, const double* sym_w, const double* sym_h,
                          const double* in, double* out, int planes, const fh_cg_state* states, const double* add,
                          double add_scale, const fh_diag_tab& dg, double* dot_part, int dot_stride) {
   fh_diag_tab none;
   memset(&none, 0, sizeof(none));
-  hipLaunchKernelGGL((k_dct_sym<INV, PPI>), grid, dim3(256), lds, st, sym_w, in, ctx->tmp_img, ctx->S, planes, states,
+  hipLaunchKernelGGL((k_dct_sym<INV, PPI, NS>), grid, dim3(256 * NS), lds, st, sym_w, in, ctx->tmp_img, ctx->S, planes, states,
                      (const double*)nullptr, 0.0, none, (double*)nullptr, 0);
-  hipLaunchKernelGGL((k_dct_sym<INV, PPI>), grid, dim3(256), lds, st, sym_h, (const double*)ctx->tmp_img, out, ctx->S, planes,
-                     states, add, add_scale, dg, dot_part, dot_stride);
+  hipLaunchKernelGGL((k_dct_sym<INV, PPI, NS>), grid, dim3(256 * NS), lds, st, sym_h, (const double*)ctx->tmp_img, out, ctx->S,
+                     planes, states, add, add_scale, dg, dot_part, dot_stride);
 }
 
 // the two symmetric passes: tmp = (X P_w^T)^T, out = P_h X P_w^T (+ add_scale * add); sym_* = packed half bases [2][S/2][S/2]
@@ -434,23 +490,23 @@ static int dct2d_launch_sym(fh_context* ctx, const double* in, double* out, int 
   const int S = ctx->S, H = S / 2;
   if (planes > ctx->planes_max || S % 128 != 0) return FH_ESIZE;
   if (ppi != 1 && ppi != 3) return FH_EINVAL;
-  const int gx = S / 32, gy = H / 32;
-  int gz = 256 / (gx * gy);
-  if (gz < (planes + 7) / 8) gz = (planes + 7) / 8;
-  if (gz > planes) gz = planes;
-  if (gz < 1) gz = 1;
   if (H % 64 != 0) return FH_ESIZE;  // K chunks of 64
-  const size_t lds = ((size_t)2 * 32 * (H + 2) + (size_t)2 * 2 * 32 * 66) * sizeof(double);
-  const dim3 grid(gx, gy, gz);
+  const dct_sym_plan_t pn = dct_sym_plan(S, planes);
+  if (pn.lds_bytes > 140 * 1024) return FH_ESIZE;  // (the opt-in of set_kernel_attributes)
+  const int gx = pn.gx, gy = pn.gy;
+  const dim3 grid(gx, gy, pn.gz);
   fh_diag_tab dg;
   memset(&dg, 0, sizeof(dg));
   if (diag != nullptr)
     for (int i = 0; i < diag->nimg && i < FH_MAX_BATCH; ++i) dg.D[i] = diag->D[i];
   if (add == nullptr || ppi * gx * gy > 256) dot_part = nullptr;  // (the consumer sums <= 256 partials per image)
   if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? ppi * gx * gy : 0;
-  const auto pair = ppi == 1 ? (inverse ? dct_sym_pair<true, 1> : dct_sym_pair<false, 1>)  // (one plane per image: image = plane)
-                            : (inverse ? dct_sym_pair<true, 3> : dct_sym_pair<false, 3>);
-  pair(ctx, grid, lds, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
+  const auto pair = pn.ns == 2
+                        ? (ppi == 1 ? (inverse ? dct_sym_pair<true, 1, 2> : dct_sym_pair<false, 1, 2>)
+                                    : (inverse ? dct_sym_pair<true, 3, 2> : dct_sym_pair<false, 3, 2>))
+                        : (ppi == 1 ? (inverse ? dct_sym_pair<true, 1, 1> : dct_sym_pair<false, 1, 1>)  // (one plane per image)
+                                    : (inverse ? dct_sym_pair<true, 3, 1> : dct_sym_pair<false, 3, 1>));
+  pair(ctx, grid, (size_t)pn.lds_bytes, st, sym_w, sym_h, in, out, planes, states, add, add_scale, dg, dot_part, dot_stride);
   FH_LAUNCH_CHECK();
   return 0;
 }
@@ -2572,8 +2628,11 @@ __global__ __launch_bounds__(256) void k_cg_step2(const double* __restrict__ r, 
 // Every kernel of this file that needs more than 64 KiB of dynamic LDS gets its opt-in here, from fh_context_create (under
 // g_capture_mu, before any launch and outside any capture): no kernel of this file launches without a context.
 static int set_kernel_attributes() {
-  const void* const at_140k[] = {(const void*)k_dct_sym<false, 3>, (const void*)k_dct_sym<true, 3>, (const void*)k_dct_sym<false, 1>,
-                                 (const void*)k_dct_sym<true, 1>, (const void*)k_woodbury_inner};
+  const void* const at_140k[] = {(const void*)k_dct_sym<false, 3>,    (const void*)k_dct_sym<true, 3>,
+                                 (const void*)k_dct_sym<false, 1>,    (const void*)k_dct_sym<true, 1>,
+                                 (const void*)k_dct_sym<false, 3, 2>, (const void*)k_dct_sym<true, 3, 2>,
+                                 (const void*)k_dct_sym<false, 1, 2>, (const void*)k_dct_sym<true, 1, 2>,
+                                 (const void*)k_woodbury_inner};
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
   for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
@@ -2725,6 +2784,13 @@ int fh_context_status(fh_context* ctx, void* stream) {
   FH_CHECK(hipMemsetAsync(ctx->sync, 0, sizeof(unsigned int) * (FH_MAX_BATCH * kSyncStride + 32), (hipStream_t)stream));
   FH_CHECK(hipStreamSynchronize((hipStream_t)stream));
   return FH_ESYNC;
+}
+
+int fh_dct_sym_plan(int S, int planes, int* gx, int* gy, int* gz, int* ns, int64_t* lds_bytes) {
+  if (S < 128 || S % 128 != 0 || planes < 1 || !gx || !gy || !gz || !ns || !lds_bytes) return FH_EINVAL;
+  const dct_sym_plan_t pn = dct_sym_plan(S, planes);
+  *gx = pn.gx, *gy = pn.gy, *gz = pn.gz, *ns = pn.ns, *lds_bytes = pn.lds_bytes;
+  return 0;
 }
 
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream) {

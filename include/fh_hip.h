@@ -58,6 +58,12 @@ int fh_debug_read_stamps(fh_context* ctx, unsigned long long* out_host, int coun
  * conditioning_utils/online_update_bfgs.py:351-374.  in may equal out. */
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream);
 
+/* Launch plan of the symmetric DCT passes fh_dct2d and the CG operator run at side S (a multiple of 128) over `planes`
+ * planes: grid (gx, gy, gz) of 256 * ns threads with lds_bytes of dynamic LDS; ns plane streams per workgroup, stream s
+ * of the gz * ns walks planes s, s + gz * ns, ... (at most 8).  ns = 2 exactly when planes * gx * gy > 256.  Host
+ * arithmetic only: needs no context and no device. */
+int fh_dct_sym_plan(int S, int planes, int* gx, int* gy, int* gz, int* ns, int64_t* lds_bytes);
+
 /* Adds the DCT moments of n images to running sums: the accumulation loop of the DCT-variance prior,
  * do_frequency_analysis.py:40-44.  imgs: uint8 [n][3][S][S] (4-byte aligned); work: n*3*S*S doubles of scratch;
  * sum, sumsq: double [3][S][S], read and written (16-byte aligned, zeroed by the caller before the first call).
