@@ -94,6 +94,7 @@ _SIGS = {
     "fh_conv2d_x6_nhwc_gn": ([c_dp, c_dp, c_dp, c_dp, c_dp, c_dp] + [C.c_int] * 10 + [C.POINTER(FhGnEpilogue), C.c_void_p],
                              C.c_int),
     "fh_conv2d_x6_gn_chunks": ([C.c_int] * 10, C.c_int),
+    "fh_conv2d_x6_plan": ([C.c_int] * 10 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_groupnorm_finalize": ([c_dp, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p], C.c_int),
     "fh_groupnorm_bwd_table": ([c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_groupnorm_bwd_apply": ([c_dp] * 8 + [C.c_int, c_dp] + [C.c_int] * 5 + [C.c_void_p], C.c_int),

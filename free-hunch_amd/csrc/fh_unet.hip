@@ -535,7 +535,7 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_x6(ConvArgsX a) {
 
 // ------------------------------------------------------------------------------------------------
 // Row-reuse form of k_conv_x6 for 3x3 / stride 1 / pad 1 layers whose 128-pixel tiles are whole row segments (W % 128 == 0,
-// or W = 64 / 32 with the tile spanning 2 / 4 full rows): the 256^2 ... 32^2 levels of the UNet.  The three taps of a kernel row read the same
+// or W = 64 / 32 / 16 with the tile spanning 2 / 4 / 8 full rows; 16 in the split-K form only): the 256^2 ... 16^2 levels of the UNet.  The three taps of a kernel row read the same
 // input pixels shifted by one, so the activation tile is staged ONCE per (channel chunk, kernel row) with a one-pixel halo
 // on each side of every row segment (130 ... 136 pixels) and the kx = 0, 1, 2 products read it at row offsets 0, 1, 2: global loads, bf16 splits and
 // LDS writes of the activation operand drop 3x; only the weight tile changes per tap.  Same tile shape as the generic
@@ -560,8 +560,15 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_x6(ConvArgsX a) {
 // last used), and the one barrier per tap waits with an explicit `s_waitcnt vmcnt(n)` that leaves the younger DMA / loads
 // in flight (a __syncthreads() would drain them).  Every wave issues exactly one DMA per tap and IA (+2 table) loads per
 // row, unconditionally, so the counts are exact.
-template <int SEGW, bool NORM = false, int BM = 128, int NP = 3, int GL = 0, bool F16 = false>  // SEGW: pixels per row segment of the tile (W, capped at BM)
+// SPLIT (split-K, register-staged 128-pixel tile only; LDS-DMA weights with one workgroup per CU were measured on these
+// grids and lost to this form, profiles/splitk_reuse.md): the workgroup runs the chunks [c_begin, c_end) of slice blockIdx.z,
+// the same ranges as k_conv_x6's, and leaves its raw accumulator in the workspace slab of the slice for k_splitk_reduce.  A
+// range may start or end inside a kernel row: the row of (cc, ky) of c_begin is staged whatever its kx, and restaged whenever
+// kx returns to 0.  Per accumulator element the MFMAs, their operands and their order are those of k_conv_x6 (chunk order
+// (cc, ky, kx), halo and padding pixels exact zeros like its masked loads), so the two kernels agree to the last bit.
+template <int SEGW, bool NORM = false, int BM = 128, int NP = 3, int GL = 0, bool F16 = false, bool SPLIT = false>  // SEGW: pixels per row segment of the tile (W, capped at BM)
 __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
+  static_assert(!SPLIT || (GL == 0 && BM == 128 && !NORM), "split-K: the register-staged 128-pixel tile, plain input");
   constexpr int MI = 2, NI = 1, WN = 4, T = 4 * BM;
   constexpr int NSEG = BM / SEGW, SP = SEGW + 2;  // row segments per tile, staged pixels per segment (one halo each side)
   constexpr int BN = 128, AR = NSEG * SP;
@@ -588,6 +595,8 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
   const int n0 = tile_n * BN;
   const int cpt = a.Cin / kBK;
   const int nchunks = cpt * 9;
+  const int c_begin = SPLIT ? (int)((int64_t)nchunks * blockIdx.z / a.ksplit) : 0;
+  const int c_end = SPLIT ? (int)((int64_t)nchunks * (blockIdx.z + 1) / a.ksplit) : nchunks;
   // the tile is NSEG consecutive row segments of one image: rows py .. py + NSEG - 1, columns px0 .. px0 + SEGW - 1
   const int pn = (int)(m0 / ((int64_t)a.H * a.W));
   const int rem = (int)(m0 % ((int64_t)a.H * a.W));
@@ -835,16 +844,16 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
         __syncthreads();
       }
     }
-  } else {
-  load_a(0, 0);
-  load_b(0, 0);
+  } else if (!SPLIT || c_begin < c_end) {  // (a split-K slice of a short K range may be empty: its slab is zeros)
+  load_a(c_begin / 9, (c_begin / 3) % 3);
+  load_b(c_begin / 9, c_begin % 9);
   store_a();
   store_b(0);
   __syncthreads();
-  for (int c = 0; c < nchunks; ++c) {
+  for (int c = c_begin; c < c_end; ++c) {
     const int kx = c % 3;
     const int nx = c + 1;
-    const bool more = nx < nchunks;
+    const bool more = nx < c_end;
     const bool new_row = more && (nx % 3 == 0);
     if (more) {
       const int ncc = nx / 9, nky = (nx / 3) % 3, nkx = nx % 3;
@@ -863,14 +872,15 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
   }
   }
   const int64_t M = (int64_t)a.N * a.Ho * a.Wo;
-  const bool gn = a.gn_partial != nullptr;
+  const bool gn = !SPLIT && a.gn_partial != nullptr;
+  float* dst = SPLIT ? a.ws + (int64_t)blockIdx.z * M * a.Cout : a.out;  // split-K: raw partial sums, k_splitk_reduce finishes
   GnAcc gsum[NI];
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
     gsum[j].s0 = gsum[j].s1 = 0.f;
     const int co = n0 + wn + j * 32 + lr;
     if (co >= a.Cout) continue;
-    const float bv = a.bias != nullptr ? a.bias[co] : 0.f;
+    const float bv = (!SPLIT && a.bias != nullptr) ? a.bias[co] : 0.f;
     float tb[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (gn && a.gn_mode == 1) {
 #pragma unroll
@@ -885,8 +895,8 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
           float v = acc[i][j][r];
           if (F16 && NP == 2) v = v * ssc.inv_in * ssc.winv;
           v += bv;
-          if (a.res != nullptr) v += a.res[row * a.Cout + co];
-          a.out[row * a.Cout + co] = v;
+          if (!SPLIT && a.res != nullptr) v += a.res[row * a.Cout + co];
+          dst[row * a.Cout + co] = v;
           if (gn) gn_accum(a, gsum[j], v, row, co, tb);
         }
       }
@@ -1874,10 +1884,17 @@ struct X6Plan {
   int bm, bn;  // output tile: pixels x channels (k_conv_x6r: bn = 128; k_conv_x6: 128 x 128, 64 x 128 or 64 x 64)
   int segw;    // k_conv_x6r: pixels per row segment of the tile
   int gl;      // k_conv_x6r: 1 = weight tile by LDS-DMA (the 256-pixel tile), 0 = staged through registers
+  bool split;  // k_conv_x6r: the split-K form (ksplit > 1), partial sums to the workspace
   dim3 grid, block;
   bool norm;   // k_conv_x6r: GroupNorm(+SiLU) applied while the input tile is staged (fh_conv2d_x6_norm_nhwc)
   int gn_bm;   // tile height the group-sum epilogue sees, 0 where the epilogue does not apply
 };
+
+// FH_CONV_SPLITK_REUSE=0 plans the generic kernel for every split-K launch (A/B switch, read once per process)
+bool splitk_reuse_enabled() {
+  static const bool on = !(getenv("FH_CONV_SPLITK_REUSE") != nullptr && atoi(getenv("FH_CONV_SPLITK_REUSE")) == 0);
+  return on;
+}
 
 X6Plan x6_plan(int ksplit, int N, int H, int W, int /*Cin: no tile depends on it*/, int Cout, int KH, int KW, int pad,
                int stride, bool norm) {
@@ -1912,7 +1929,18 @@ X6Plan x6_plan(int ksplit, int N, int H, int W, int /*Cin: no tile depends on it
     p.gl = p.bm == 256;
   } else if (ksplit > 1 && Cout > 64 && b128 * ksplit >= 256) {
     // small grids: 128 x 128 tiles (21 flop per byte pulled from L2 instead of 12.8) once split-K still fills the chip
+    // 3 x 3 / stride 1 / pad 1 layers whose 128-pixel tiles are whole row segments of one image take the row-reuse kernel
+    // in its split-K form: same grid, same K ranges, same partial slabs, two thirds of the activation staging gone
     p.bm = 128;
+    const bool r3 = KH == 3 && KW == 3 && pad == 1 && stride == 1 && ((int64_t)H * W) % 128 == 0 && splitk_reuse_enabled();
+    if (r3 && W % 128 == 0)
+      p.reuse = p.split = true, p.segw = 128;
+    else if (r3 && W == 64 && H % 2 == 0)
+      p.reuse = p.split = true, p.segw = 64;
+    else if (r3 && W == 32 && H % 4 == 0)
+      p.reuse = p.split = true, p.segw = 32;
+    else if (r3 && W == 16 && H % 8 == 0)
+      p.reuse = p.split = true, p.segw = 16;
   } else if (ksplit == 1 && Cout > 64 && ((M + 63) / 64) * nb128 >= 256) {
     p.bm = 64;
   } else {
@@ -1926,15 +1954,15 @@ X6Plan x6_plan(int ksplit, int N, int H, int W, int /*Cin: no tile depends on it
 }
 
 // the five precision instantiations of one tile (fh_unet_set_precision)
-template <int SEGW, bool NORM, int BM, int GL>
+template <int SEGW, bool NORM, int BM, int GL, bool SPLIT = false>
 void launch_x6r(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
   switch (g_conv_np) {
-    case 1: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL>), p.grid, p.block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL>), p.grid, p.block, 0, st, a); break;
-    case 16: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL, true>), p.grid, p.block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL, false, SPLIT>), p.grid, p.block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL, false, SPLIT>), p.grid, p.block, 0, st, a); break;
+    case 16: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 1, GL, true, SPLIT>), p.grid, p.block, 0, st, a); break;
     // half-split with LDS-DMA weights: three-slot weight ring + double-buffered activations (GL = 2)
-    case 32: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL == 1 ? 2 : GL, true>), p.grid, p.block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 3, GL>), p.grid, p.block, 0, st, a); break;
+    case 32: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 2, GL == 1 ? 2 : GL, true, SPLIT>), p.grid, p.block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, BM, 3, GL, false, SPLIT>), p.grid, p.block, 0, st, a); break;
   }
 }
 
@@ -1961,6 +1989,18 @@ bool launch_x6r_tile(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
     case tile_key(128, 128, 0): launch_x6r<128, NORM, 128, 0>(p, st, a); return true;
     case tile_key(128, 64, 0): launch_x6r<64, NORM, 128, 0>(p, st, a); return true;
     case tile_key(128, 32, 0): launch_x6r<32, NORM, 128, 0>(p, st, a); return true;
+  }
+  return false;
+}
+
+// the split-K row-reuse tiles (BM = 128, register-staged weights; the fused GroupNorm input has no split-K form)
+bool launch_x6r_split_tile(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  if (p.norm || p.bm != 128 || p.gl != 0) return false;
+  switch (p.segw) {
+    case 128: launch_x6r<128, false, 128, 0, true>(p, st, a); return true;
+    case 64: launch_x6r<64, false, 128, 0, true>(p, st, a); return true;
+    case 32: launch_x6r<32, false, 128, 0, true>(p, st, a); return true;
+    case 16: launch_x6r<16, false, 128, 0, true>(p, st, a); return true;
   }
   return false;
 }
@@ -2058,6 +2098,17 @@ int fh_conv2d_x6_gn_chunks(int ksplit, int N, int H, int W, int Cin, int Cout, i
   return p.gn_bm ? (Ho * Wo / p.gn_bm) * ((Cout + 127) / 128) : 0;
 }
 
+int fh_conv2d_x6_plan(int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
+                      int32_t* plan) {
+  if (!plan || N < 1 || H < 1 || W < 1 || Cin < kBK || Cin % kBK != 0 || Cout < 1 || stride < 1 || ksplit < 1 || ksplit > 32)
+    return FH_EINVAL;
+  const X6Plan p = x6_plan(ksplit, N, H, W, Cin, Cout, KH, KW, pad, stride, false);
+  plan[0] = !p.reuse ? 0 : (p.split ? 2 : 1);
+  plan[1] = p.bm, plan[2] = p.bn, plan[3] = p.reuse ? p.segw : 0, plan[4] = p.reuse ? p.gl : 0;
+  plan[5] = (int32_t)p.grid.x, plan[6] = (int32_t)p.grid.y, plan[7] = (int32_t)p.grid.z;
+  return 0;
+}
+
 static int set_gn(ConvArgsX& a, const fh_gn_epilogue* epi, int chunks) {
   a.gn_partial = nullptr, a.gn_x = nullptr, a.gn_tab = nullptr, a.gn_mode = a.gn_act = a.gn_chunks = 0;
   a.in_amax = epi != nullptr ? epi->in_amax : nullptr, a.in_scale = 1.f;
@@ -2093,6 +2144,7 @@ static int conv2d_x6_launch(const float* in, bool norm, const float* ab_table, i
   }
   hipStream_t st = (hipStream_t)stream;
   const bool built = !p.reuse ? launch_x6_tile(p, st, a)
+                     : p.split ? launch_x6r_split_tile(p, st, a)
                      : p.norm ? launch_x6r_tile<true>(p, st, a)
                               : launch_x6r_tile<false>(p, st, a);
   if (!built) return FH_ESIZE;

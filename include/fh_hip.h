@@ -388,6 +388,16 @@ typedef struct fh_gn_epilogue {
   const float* in_amax; /* precision mode 4: device [FH_AMAX_SLOTS], max = max |in| (fh_absmax_f32); partial may then be null */
 } fh_gn_epilogue;
 int fh_conv2d_x6_gn_chunks(int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride);
+/* The launch fh_conv2d_x6_nhwc(ksplit, ...) will make, answered on the host (no device needed):
+ *   plan[0] kernel family: 0 = k_conv_x6 (generic), 1 = k_conv_x6r (row reuse), 2 = k_conv_x6r in its split-K form;
+ *   plan[1], plan[2] output tile bm x bn; plan[3] segw and plan[4] gl of the row-reuse kernel (0 for the generic one);
+ *   plan[5..7] grid x, y, z.
+ * Split-K launches (ksplit > 1) of 3x3 / stride 1 / pad 1 layers take family 2 when H * W is a multiple of 128 and W is a
+ * multiple of 128, or W is 64 / 32 / 16 with H divisible by 2 / 4 / 8 (128-pixel tiles of whole row segments of one image);
+ * FH_CONV_SPLITK_REUSE=0 in the environment (read once per process) keeps them on the generic kernel.  The two kernels write
+ * the same bits. */
+int fh_conv2d_x6_plan(int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
+                      int32_t* plan);
 int fh_conv2d_x6_nhwc_gn(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
                          int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
                          const fh_gn_epilogue* epi, void* stream);

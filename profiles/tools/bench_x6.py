@@ -1,5 +1,116 @@
-import os, sys, torch, math
-ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT,'tests')); sys.path.insert(0, os.path.join(ROOT,'tests','golden'))
+"""Timings of the split-bf16 convolution (fh_conv2d_x6_nhwc).
+
+    bench_x6.py                      accuracy against float64 and time against the fp32-MFMA convolution, a few large shapes
+    bench_x6.py --splitk [--batches 4,8] [--parent-root DIR] [--variants NAME=ENV=VAL,...] [--out FILE.json]
+        A/B of the split-K launches of the FFHQ-256 network's 3 x 3 layers that the plan sends to the row-reuse kernel:
+        every variant is a child process (the switch FH_CONV_SPLITK_REUSE is read once per process) timing each layer shape
+        with events on the stream, REPEATS repeats of LAUNCHES launches.  The generic kernel (switch off) runs first AND
+        last; its spread per shape is max - min over the repeats of both runs, and a gain counts where the medians differ by
+        more than that.  --parent-root: another checkout (built) whose library is timed as well.
+"""
+import json, os, statistics, subprocess, sys
+ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPEATS, LAUNCHES = 7, 100
+
+
+def splitk_child(root, shapes_file):
+    """times every (N, H, W, Ci, Co, ks) of the file with the library of checkout `root` -> JSON {key: [us per launch] * REPEATS}"""
+    sys.path.insert(0, root)
+    import torch
+    from free_hunch_amd import _lib as L
+    lib = L.load(); dev = torch.device('cuda:0'); out = {}
+    for (N, H, W, Ci, Co, ks) in json.load(open(shapes_file)):
+        g = torch.Generator().manual_seed(N + H + Ci + Co)
+        x = torch.randn(N, H, W, Ci, generator=g).to(dev)
+        wd = (torch.randn(Co, 9, Ci, generator=g) * 0.03).to(dev)
+        h = wd.to(torch.bfloat16); r = wd - h.float(); m = r.to(torch.bfloat16); l = (r - m.float()).to(torch.bfloat16)
+        wx = torch.stack([h, m, l]).reshape(3, Co, 9, Ci // 32, 32).permute(0, 2, 3, 1, 4).contiguous()
+        b = torch.zeros(Co, device=dev); o = torch.empty(N, H, W, Co, device=dev); ws = torch.empty(ks, N * H * W, Co, device=dev)
+        f = lambda: L.check(lib.fh_conv2d_x6_nhwc(x.data_ptr(), wx.data_ptr(), b.data_ptr(), None, o.data_ptr(), ws.data_ptr(), ks,
+                                                  N, H, W, Ci, Co, 3, 3, 1, 1, L.stream()), "x6")
+        for _ in range(10): f()
+        ts = []
+        for _ in range(REPEATS):
+            torch.cuda.synchronize(); e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(LAUNCHES): f()
+            e1.record(); torch.cuda.synchronize(); ts.append(1e3 * e0.elapsed_time(e1) / LAUNCHES)
+        out["%d,%d,%d,%d,%d,%d" % (N, H, W, Ci, Co, ks)] = ts
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def splitk_main(argv):
+    import ctypes
+    opt = {argv[i]: argv[i + 1] for i in range(len(argv) - 1) if argv[i].startswith("--")}
+    batches = [int(v) for v in opt.get("--batches", "4,8").split(",")]
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "tests", "golden")]
+    import make_conv_plan
+    from free_hunch_amd import _lib as L, unet
+    lib = L.load(); buf = (ctypes.c_int32 * 8)()
+    shapes = []
+    for N in batches:
+        for H, W, Ci, Co, k, stride in make_conv_plan.unet_layers(unet.FFHQ256, unet._plan):
+            ks = lib.fh_conv2d_splitk(N, H, W, Ci, Co, k, k)
+            if ks > 1 and lib.fh_conv2d_x6_plan(ks, N, H, W, Ci, Co, k, k, k // 2, stride, buf) == 0 and buf[0] == 2:
+                shapes.append((N, H, W, Ci, Co, ks))
+    import tempfile
+    fd, sf = tempfile.mkstemp(suffix=".json", prefix="bench_x6_splitk_shapes_")
+    with os.fdopen(fd, "w") as f:
+        json.dump(shapes, f)
+    variants = [("generic_first", ROOT, {"FH_CONV_SPLITK_REUSE": "0"}), ("reuse", ROOT, {})]
+    for spec in filter(None, opt.get("--variants", "").split(",")):
+        name, key, val = spec.split("=")
+        variants.append((name, ROOT, {key: val}))
+    if "--parent-root" in opt:
+        variants.append(("parent", os.path.abspath(opt["--parent-root"]), {}))
+    variants.append(("generic_last", ROOT, {"FH_CONV_SPLITK_REUSE": "0"}))
+    res = {}
+    for name, root, env in variants:
+        e = dict(os.environ, **env)
+        if not env:
+            e.pop("FH_CONV_SPLITK_REUSE", None)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--splitk-child", root, sf], env=e, stdout=subprocess.PIPE,
+                           text=True, timeout=600, check=True)
+        res[name] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        print("ran", name, flush=True)
+    others = [n for n, _r, _e in variants if not n.startswith("generic")]
+    print("us per call (split-K kernel + reduce), median of %d x %d launches; spread = max - min of the generic kernel's %d repeats"
+          % (REPEATS, LAUNCHES, 2 * REPEATS))
+    print("| N | H x W | Cin | Cout | ksplit | generic | spread | " + " | ".join("%s | gain" % n for n in others) + " |")
+    print("|---" * (7 + 2 * len(others)) + "|")
+    tot = {}
+    for N, H, W, Ci, Co, ks in shapes:
+        key = "%d,%d,%d,%d,%d,%d" % (N, H, W, Ci, Co, ks)
+        gen = res["generic_first"][key] + res["generic_last"][key]
+        gm, sp = statistics.median(gen), max(gen) - min(gen)
+        cells = []
+        t = tot.setdefault((N, W), {"generic": 0.0, "spread": 0.0, "shapes": 0})
+        t["generic"] += gm; t["spread"] += sp; t["shapes"] += 1
+        for n in others:
+            m = statistics.median(res[n][key])
+            t[n] = t.get(n, 0.0) + m
+            gain = gm - m
+            cells.append("%.1f | %+.1f%s" % (m, gain, " *" if abs(gain) > sp else ""))
+        print("| %d | %d x %d | %d | %d | %d | %.1f | %.1f | %s |" % (N, H, W, Ci, Co, ks, gm, sp, " | ".join(cells)))
+    print("\nper batch and width, summed over its shapes (one launch each); * = beyond the summed spread")
+    print("| N | W | shapes | generic | spread | " + " | ".join("%s | gain" % n for n in others) + " |")
+    print("|---" * (5 + 2 * len(others)) + "|")
+    for (N, W), t in sorted(tot.items()):
+        cells = ["%.1f | %+.1f (%+.1f %%)%s" % (t[n], t["generic"] - t[n], 100 * (t["generic"] - t[n]) / t["generic"],
+                                              " *" if abs(t["generic"] - t[n]) > t["spread"] else "") for n in others]
+        print("| %d | %d | %d | %.1f | %.1f | %s |" % (N, W, t["shapes"], t["generic"], t["spread"], " | ".join(cells)))
+    os.remove(sf)
+    if "--out" in opt:
+        json.dump({"shapes": shapes, "repeats": REPEATS, "launches": LAUNCHES, "us_per_call": res}, open(opt["--out"], "w"))
+
+
+if "--splitk-child" in sys.argv:
+    splitk_child(*sys.argv[sys.argv.index("--splitk-child") + 1:][:2]); sys.exit(0)
+if "--splitk" in sys.argv:
+    splitk_main(sys.argv[1:]); sys.exit(0)
+
+import torch, math
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT,'tests')); sys.path.insert(0, os.path.join(ROOT,'tests','golden'))
 from free_hunch_amd import _lib as L
 from test_hip_unet import wino_weights
 lib=L.load(); dev=torch.device('cuda:0')
