@@ -1250,15 +1250,22 @@ __global__ __launch_bounds__(256) void k_bgemm(GemmArgs g) {
 
 // ------------------------------------------------------------------------------------------------
 // GroupNorm (32 groups, eps 1e-5) on NHWC.  x [N][P][C], P = H*W, cg = C / 32 channels per group.
-//   k_gn_stats : one workgroup per (n, group); sums in double; writes mean / rstd (float) [N][32][2]
-//   k_gn_apply : y = act( ((x - mean) * rstd * gamma + beta) * (1 + scale[n][c]) + shift[n][c] ),  act = SiLU or id
-//   k_gn_bwd_* : dx given dy (through act, scale/shift, affine and the normalisation)
+//   k_gn_partial<MODE>  : workgroup = (n, chunk of pixels); double block partials of (sum x, sum x^2) [MODE 0] or of the
+//                         two sums of the backward [MODE 1]
+//   k_gn_finalize<MODE> : the block partials of an image -> mean / rstd [MODE 0] or the two backward sums [MODE 1], (float) [N][32][2]
+//   k_gn_stream<BWD>    : y = act( ((x - mean) * rstd * gamma + beta) * (1 + scale[n][c]) + shift[n][c] ),  act = SiLU or id
+//                         [BWD 0], or dx given dy (through act, scale/shift, affine and the normalisation) [BWD 1]
+//   k_gn_small_fwd / k_gn_small_bwd (further down): statistics and result of a small tensor in one launch
 // ------------------------------------------------------------------------------------------------
-// pixels per workgroup in the GroupNorm passes: 512, halved until the launch has >= 256 workgroups (min 32)
-static inline int gn_chunk(int N, int P) {
+// the grid of a k_gn_partial / k_gn_stream pass over [N][P][C]: pixels per workgroup (512, halved until the launch has
+// >= 256 workgroups, min 32) and workgroups per image; the launch is N * nchunks workgroups
+struct GnGrid {
+  int chunk, nchunks;
+};
+static inline GnGrid gn_grid(int N, int P) {
   int c = 512;
   while (c > 32 && (int64_t)N * ((P + c - 1) / c) < 256) c >>= 1;
-  return c;
+  return {c, (P + c - 1) / c};
 }
 
 // Shared skeleton of the two statistics passes.  Workgroup = (image n, chunk of kGnChunk pixels); a thread owns one
@@ -1520,6 +1527,38 @@ __global__ __launch_bounds__(256) void k_gn_stream(const float* __restrict__ x, 
       if (mx1) atomicMax(amax + FH_AMAX_SLOTS + slot, mx1);
     }
   }
+}
+
+// The two launch sequences the GroupNorm entry points are composed of (grid: gn_grid).
+// k_gn_partial<MODE> + k_gn_finalize<MODE>: block partials into `part` (fh_groupnorm_scratch_doubles), then out [N][32][2] =
+// (mean, rstd) of x [MODE 0] or the two sums of the backward [MODE 1]
+template <int MODE>
+static void gn_launch_sums(hipStream_t st, const float* x, const float* dy, const float* stats, const float* gamma,
+                           const float* beta, const float* scale, const float* shift, int ss_stride, double* part, float* out,
+                           int N, int P, int C, int act) {
+  const GnGrid g = gn_grid(N, P);
+  hipLaunchKernelGGL(k_gn_partial<MODE>, dim3(N * g.nchunks), dim3(256), 0, st, x, dy, stats, gamma, beta, scale, shift,
+                     ss_stride, part, P, C, act, g.nchunks, g.chunk);
+  hipLaunchKernelGGL(k_gn_finalize<MODE>, dim3(N), dim3(1024), 0, st, (const double*)part, out, g.nchunks,
+                     (double)P * (C / 32));
+}
+
+// k_gn_stream<1>, the streaming pass of the backward, with the operands of fh_groupnorm_bwd_apply_ex (null / 0 = without)
+static void gn_launch_bwd_stream(hipStream_t st, const float* x, const float* dy, const float* stats, const float* sums,
+                                 const float* gamma, const float* beta, const float* scale, const float* shift, int ss_stride,
+                                 const float* acc_src, const float* add2, float* dx, float* dx2, int csplit, int N, int P, int C,
+                                 int act, float* amax2) {
+  const GnGrid g = gn_grid(N, P);
+  static const int nt_env = getenv("FH_GN_NT") ? atoi(getenv("FH_GN_NT")) : 1;  // streaming loads of the read-once gradients beyond the Infinity Cache (measured 233 -> 218 us at 8 x 256^2 x 128; 0 = off)
+  const int nt = nt_env && (int64_t)N * P * C * 4 > ((int64_t)200 << 20);
+  if (amax2 != nullptr)
+    hipLaunchKernelGGL((k_gn_stream<1, true>), dim3(N * g.nchunks), dim3(256), 0, st, x, dy, stats, sums, gamma, beta, scale,
+                       shift, ss_stride, dx, P, C, act, acc_src != nullptr ? 1 : 0, g.nchunks, g.chunk, acc_src, add2, dx2,
+                       csplit, reinterpret_cast<unsigned*>(amax2), nt);
+  else
+    hipLaunchKernelGGL((k_gn_stream<1, false>), dim3(N * g.nchunks), dim3(256), 0, st, x, dy, stats, sums, gamma, beta, scale,
+                       shift, ss_stride, dx, P, C, act, acc_src != nullptr ? 1 : 0, g.nchunks, g.chunk, acc_src, add2, dx2,
+                       csplit, (unsigned*)nullptr, nt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2265,22 +2304,11 @@ int fh_bgemm_f32(const float* A, const float* B, float* C, int M, int N, int K, 
   return 0;
 }
 
-int64_t fh_groupnorm_scratch_doubles(int N, int P) {
-  const int chunk = gn_chunk(N, P);
-  return (int64_t)N * ((P + chunk - 1) / chunk) * 64;
-}
+int64_t fh_groupnorm_scratch_doubles(int N, int P) { return (int64_t)N * gn_grid(N, P).nchunks * 64; }
 
 int fh_groupnorm_stats(const float* x, float* stats, double* scratch, int N, int P, int C, void* stream) {
   if (!x || !stats || !scratch || C % 32 != 0) return FH_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  double* part = scratch;
-  hipLaunchKernelGGL(k_gn_partial<0>, dim3(N * nchunks), dim3(256), 0, st, x, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, 0, part, P, C, 0, nchunks, kGnChunk);
-  hipLaunchKernelGGL(k_gn_finalize<0>, dim3(N), dim3(1024), 0, st, (const double*)part, stats, nchunks,
-                     (double)P * (C / 32));
+  gn_launch_sums<0>((hipStream_t)stream, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, scratch, stats, N, P, C, 0);
   FH_LAUNCH_CHECK();
   return 0;
 }
@@ -2288,29 +2316,22 @@ int fh_groupnorm_stats(const float* x, float* stats, double* scratch, int N, int
 int fh_groupnorm_apply(const float* x, const float* stats, const float* gamma, const float* beta, const float* scale,
                        const float* shift, int ss_stride, float* y, int N, int P, int C, int act, void* stream) {
   if (!x || !stats || !gamma || !beta || !y || C % 32 != 0) return FH_EINVAL;
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  hipLaunchKernelGGL(k_gn_stream<0>, dim3(N * nchunks), dim3(256), 0, (hipStream_t)stream, x, (const float*)nullptr,
-                     stats, (const float*)nullptr, gamma, beta, scale, shift, ss_stride, y, P, C, act, 0, nchunks,
-                     kGnChunk);
+  const GnGrid g = gn_grid(N, P);
+  hipLaunchKernelGGL(k_gn_stream<0>, dim3(N * g.nchunks), dim3(256), 0, (hipStream_t)stream, x, (const float*)nullptr,
+                     stats, (const float*)nullptr, gamma, beta, scale, shift, ss_stride, y, P, C, act, 0, g.nchunks, g.chunk);
   FH_LAUNCH_CHECK();
   return 0;
 }
 
+// fh_groupnorm_bwd_sums, then fh_groupnorm_bwd_apply (accumulate: dx += instead of dx =)
 int fh_groupnorm_bwd(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta,
                      const float* scale, const float* shift, int ss_stride, float* sums, double* scratch, float* dx, int N,
                      int P, int C, int act, int accumulate, void* stream) {
   if (!x || !dy || !stats || !gamma || !beta || !sums || !scratch || !dx || C % 32 != 0) return FH_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  double* part = scratch;
-  hipLaunchKernelGGL(k_gn_partial<1>, dim3(N * nchunks), dim3(256), 0, st, x, dy, stats, gamma, beta, scale, shift,
-                     ss_stride, part, P, C, act, nchunks, kGnChunk);
-  hipLaunchKernelGGL(k_gn_finalize<1>, dim3(N), dim3(1024), 0, st, (const double*)part, sums, nchunks,
-                     (double)P * (C / 32));
-  hipLaunchKernelGGL(k_gn_stream<1>, dim3(N * nchunks), dim3(256), 0, st, x, dy, stats, (const float*)sums, gamma, beta,
-                     scale, shift, ss_stride, dx, P, C, act, accumulate, nchunks, kGnChunk);
+  gn_launch_sums<1>(st, x, dy, stats, gamma, beta, scale, shift, ss_stride, scratch, sums, N, P, C, act);
+  gn_launch_bwd_stream(st, x, dy, stats, sums, gamma, beta, scale, shift, ss_stride, accumulate ? dx : nullptr, nullptr, dx,
+                       nullptr, 0, N, P, C, act, nullptr);
   FH_LAUNCH_CHECK();
   return 0;
 }
@@ -2362,13 +2383,8 @@ int fh_groupnorm_bwd_table(const float* stats, const float* gamma, const float* 
 int fh_groupnorm_bwd_apply(const float* x, const float* dy, const float* stats, const float* sums, const float* gamma,
                            const float* beta, const float* scale, const float* shift, int ss_stride, float* dx, int N, int P,
                            int C, int act, int accumulate, void* stream) {
-  if (!x || !dy || !stats || !sums || !gamma || !beta || !dx || C % 32 != 0) return FH_EINVAL;
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  hipLaunchKernelGGL(k_gn_stream<1>, dim3(N * nchunks), dim3(256), 0, (hipStream_t)stream, x, dy, stats, sums, gamma, beta,
-                     scale, shift, ss_stride, dx, P, C, act, accumulate, nchunks, kGnChunk);
-  FH_LAUNCH_CHECK();
-  return 0;
+  return fh_groupnorm_bwd_apply_ex(x, dy, stats, sums, gamma, beta, scale, shift, ss_stride, accumulate ? dx : nullptr, nullptr,
+                                   dx, nullptr, 0, N, P, C, act, nullptr, stream);  // (the same argument checks)
 }
 
 // the two reductions of fh_groupnorm_bwd alone: sums [N][32][2] = (mean g, mean g xhat)
@@ -2376,40 +2392,21 @@ int fh_groupnorm_bwd_sums(const float* x, const float* dy, const float* stats, c
                           const float* scale, const float* shift, int ss_stride, float* sums, double* scratch, int N, int P,
                           int C, int act, void* stream) {
   if (!x || !dy || !stats || !gamma || !beta || !sums || !scratch || C % 32 != 0) return FH_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  hipLaunchKernelGGL(k_gn_partial<1>, dim3(N * nchunks), dim3(256), 0, st, x, dy, stats, gamma, beta, scale, shift,
-                     ss_stride, scratch, P, C, act, nchunks, kGnChunk);
-  hipLaunchKernelGGL(k_gn_finalize<1>, dim3(N), dim3(1024), 0, st, (const double*)scratch, sums, nchunks,
-                     (double)P * (C / 32));
+  gn_launch_sums<1>((hipStream_t)stream, x, dy, stats, gamma, beta, scale, shift, ss_stride, scratch, sums, N, P, C, act);
   FH_LAUNCH_CHECK();
   return 0;
 }
 
-// fh_groupnorm_bwd_apply with the two extras of k_gn_stream<1>: acc_src (addend read from another tensor than dx), add2 (a
-// second addend) and the split destination (dx: [.., csplit], dx2: [.., C - csplit]); any of them may be null / 0
+// fh_groupnorm_bwd_apply with the extras of k_gn_stream<1>: acc_src (the addend, read from dx itself or from another tensor),
+// add2 (a second addend) and the split destination (dx: [.., csplit], dx2: [.., C - csplit]); any of them may be null / 0
 int fh_groupnorm_bwd_apply_ex(const float* x, const float* dy, const float* stats, const float* sums, const float* gamma,
                               const float* beta, const float* scale, const float* shift, int ss_stride, const float* acc_src,
                               const float* add2, float* dx, float* dx2, int csplit, int N, int P, int C, int act, float* amax2,
                               void* stream) {
   if (!x || !dy || !stats || !sums || !gamma || !beta || !dx || C % 32 != 0) return FH_EINVAL;
   if (dx2 != nullptr && (csplit <= 0 || csplit >= C || csplit % 4 != 0)) return FH_EINVAL;
-  if (dx2 == nullptr && acc_src != nullptr && acc_src != dx) {
-    // (without a split the addend may still come from elsewhere: dx is written, acc_src only read)
-  }
-  const int kGnChunk = gn_chunk(N, P);
-  const int nchunks = (P + kGnChunk - 1) / kGnChunk;
-  static const int nt_env = getenv("FH_GN_NT") ? atoi(getenv("FH_GN_NT")) : 1;  // streaming loads of the read-once gradients beyond the Infinity Cache (measured 233 -> 218 us at 8 x 256^2 x 128; 0 = off)
-  const int nt = nt_env && (int64_t)N * P * C * 4 > ((int64_t)200 << 20);
-  if (amax2 != nullptr)
-    hipLaunchKernelGGL((k_gn_stream<1, true>), dim3(N * nchunks), dim3(256), 0, (hipStream_t)stream, x, dy, stats, sums, gamma,
-                       beta, scale, shift, ss_stride, dx, P, C, act, acc_src != nullptr ? 1 : 0, nchunks, kGnChunk, acc_src, add2,
-                       dx2, csplit, reinterpret_cast<unsigned*>(amax2), nt);
-  else
-    hipLaunchKernelGGL((k_gn_stream<1, false>), dim3(N * nchunks), dim3(256), 0, (hipStream_t)stream, x, dy, stats, sums, gamma,
-                       beta, scale, shift, ss_stride, dx, P, C, act, acc_src != nullptr ? 1 : 0, nchunks, kGnChunk, acc_src, add2,
-                       dx2, csplit, (unsigned*)nullptr, nt);
+  gn_launch_bwd_stream((hipStream_t)stream, x, dy, stats, sums, gamma, beta, scale, shift, ss_stride, acc_src, add2, dx, dx2,
+                       csplit, N, P, C, act, amax2);
   FH_LAUNCH_CHECK();
   return 0;
 }

@@ -30,6 +30,16 @@ def _pad_to(n, m):
     return (n + m - 1) // m * m
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _switch(name):
+    """The A/B switch FH_<name> of the dispatch (GN_EPILOGUE, GN_SMALL, GN_FUSE, ATTN_FUSED, GLUE_FOLD): on unless the
+    variable is "0".  Read at every call: the GPU tests flip the switches inside one process."""
+    return os.environ.get("FH_" + name, "1") != "0"
+
+
 def _wino(w):
     """[rows][ky][kx][K] -> [4][rows][ky][K]: u = (w0, (w0+w1+w2)/2, (w0-w1+w2)/2, w2) over kx"""
     w0, w1, w2 = w[:, :, 0], w[:, :, 1], w[:, :, 2]
@@ -183,6 +193,14 @@ class HipOps:
         self._tls = threading.local()  # emb_key: the timestep tuple of the call running on THIS host thread
 
     # ---------------------------------------------------------------- kernel wrappers
+    # Three hand-offs ride on the tensors themselves (attributes of the torch.Tensor a wrapper returns):
+    #   _fh_gn       set by `_conv` / `_gn_conv` on a convolution's output whose launch left group-sum partials (the
+    #                [partial, chunks] of `_epilogue`); read by `_gn_stats` (finalize instead of a statistics pass) and by
+    #                `_gn`, which keeps such a tensor off the one-launch kernel
+    #   _fh_gn_sums  set by `_dgrad` on an input gradient whose launch left the backward sums of the GroupNorm it is the
+    #                dL/dy of; read by `_gn_bwd` (no sums pass, no one-launch kernel)
+    #   _fh_amax     set by `_gn_bwd` on dx (, dx2) in the half-split mode: the tensor's magnitude; read by `_launch_mode`
+    #                (a 1 x 1 input gradient takes the half-split mode only with it) and `_amax` (no magnitude pass)
     def _launch_mode(self, c, stride=1, x=None):
         """fh_unet_set_precision code of ONE split-kernel launch.  The half-split mode (4) covers the 3 x 3 / stride 1
         layers (97 % of the matrix work) and the 1 x 1 ones whose input `x` arrives with its magnitude (`_fh_amax`, left by the
@@ -211,26 +229,35 @@ class HipOps:
         _lib.check(self.lib.fh_absmax_f32(x.data_ptr(), x.numel(), out.data_ptr(), _lib.stream()), "fh_absmax_f32")
         return out
 
+    def _conv_route(self, c, fwd, x, res, bias, mode, gn=None):
+        """The stride-1 convolution of `c` on x [N][H][W][K] in either direction (`fwd`: forward weights, else the
+        input-gradient ones; rows = output channels of that direction) by the route its shape takes: Winograd F(2,3), the
+        thin-output kernel, else the implicit GEMM of `conv_launch` with the group-sum epilogue request (mode, gn).
+        Returns (output, what the epilogue left behind or None)."""
+        N, H, W, K = x.shape
+        rows, w32, wu = (c.co, c.wf, c.wu_f) if fwd else (c.ci, c.wd, c.wu_d)
+        wino = wu is not None and _use_wino(N, H, W, K, rows)
+        thin = not wino and rows <= 8 and c.kh == 3 and c.kw == 3 and res is None and H * W >= 4096
+        if not (wino or thin):
+            return conv_launch(self.lib, c, fwd, x, res, bias, 1, ops=self, mode=mode, gn=gn)
+        what = "" if fwd else "(dgrad)"
+        out = torch.empty(N, H, W, rows, dtype=torch.float32, device=x.device)
+        if wino:
+            _lib.check(self.lib.fh_conv3x3_wino_nhwc(x.data_ptr(), wu.data_ptr(), _ptr(bias), _ptr(res), out.data_ptr(), N, H,
+                                                     W, K, rows, _lib.stream()), "fh_conv3x3_wino_nhwc" + what)
+        else:
+            _lib.check(self.lib.fh_conv3x3_thin_nhwc(x.data_ptr(), w32.data_ptr(), _ptr(bias), out.data_ptr(), N, H, W, K,
+                                                     rows, _lib.stream()), "fh_conv3x3_thin_nhwc" + what)
+        return out, None
+
     def _conv(self, name, x, res=None, bias_override=None, stride=1):
         c = self.conv[name]
-        N, H, W, Ci = x.shape
-        assert Ci == c.ci_p, (name, x.shape, c.ci_p)
+        assert x.shape[-1] == c.ci_p, (name, x.shape, c.ci_p)
         b = c.b if bias_override is None else bias_override
         if stride != 1:  # Downsample(use_conv=True), openai_unet.py:131: 3x3, stride 2, padding 1
             return conv_launch(self.lib, c, True, x, res, b, stride, ops=self)[0]
-        if c.wu_f is not None and _use_wino(N, H, W, Ci, c.co):
-            out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
-            _lib.check(self.lib.fh_conv3x3_wino_nhwc(x.data_ptr(), c.wu_f.data_ptr(), b.data_ptr(),
-                                                     None if res is None else res.data_ptr(), out.data_ptr(), N, H, W,
-                                                     Ci, c.co, _lib.stream()), "fh_conv3x3_wino_nhwc")
-            return out
-        if c.co <= 8 and c.kh == 3 and c.kw == 3 and res is None and H * W >= 4096:
-            out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
-            _lib.check(self.lib.fh_conv3x3_thin_nhwc(x.data_ptr(), c.wf.data_ptr(), b.data_ptr(), out.data_ptr(), N, H, W,
-                                                     Ci, c.co, _lib.stream()), "fh_conv3x3_thin_nhwc")
-            return out
         # group-sum epilogue: the statistics of a GroupNorm applied to this output come out of the convolution itself
-        out, keep = conv_launch(self.lib, c, True, x, res, b, 1, ops=self, mode=0)
+        out, keep = self._conv_route(c, True, x, res, b, mode=0)
         if keep is not None:
             out._fh_gn = keep
         return out
@@ -245,20 +272,9 @@ class HipOps:
             gp = torch.zeros(N, H, W, c.co_p, dtype=torch.float32, device=g.device)
             gp[..., :Co] = g
             g = gp
-        if c.wu_d is not None and _use_wino(N, H, W, c.co_p, c.ci):
-            out = torch.empty(N, H, W, c.ci, dtype=torch.float32, device=g.device)
-            _lib.check(self.lib.fh_conv3x3_wino_nhwc(g.data_ptr(), c.wu_d.data_ptr(), None,
-                                                     None if res is None else res.data_ptr(), out.data_ptr(), N, H, W,
-                                                     c.co_p, c.ci, _lib.stream()), "fh_conv3x3_wino_nhwc(dgrad)")
-            return out
-        if c.ci <= 8 and c.kh == 3 and c.kw == 3 and res is None and H * W >= 4096:
-            out = torch.empty(N, H, W, c.ci, dtype=torch.float32, device=g.device)
-            _lib.check(self.lib.fh_conv3x3_thin_nhwc(g.data_ptr(), c.wd.data_ptr(), None, out.data_ptr(), N, H, W, c.co_p,
-                                                     c.ci, _lib.stream()), "fh_conv3x3_thin_nhwc(dgrad)")
-            return out
         if gn is not None and tuple(gn[1].shape) != (N, H, W, c.ci):
             gn = None
-        out, keep = conv_launch(self.lib, c, False, g, res, None, 1, ops=self, mode=1, gn=gn)
+        out, keep = self._conv_route(c, False, g, res, None, mode=1, gn=gn)
         if keep is not None:
             partial, chunks = keep[0], keep[1]
             sums = torch.empty(N, 32, 2, dtype=torch.float32, device=g.device)
@@ -267,13 +283,18 @@ class HipOps:
             out._fh_gn_sums = sums
         return out
 
+    def _gn_operands(self, name, scale=None, shift=None):
+        """the five operands every GroupNorm pass takes for norm `name`: gamma, beta, scale, shift, ss_stride"""
+        return (self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(), _ptr(scale), _ptr(shift),
+                0 if scale is None else scale.stride(0))
+
     def _epilogue(self, ks, N, H, W, Ci, Co, kh, kw, pad, mode, gn=None, amax=None):
         """fh_gn_epilogue for the split-bf16 convolution launch of this layer, or (None, None) where the launch has none
         (split-K, thin output, ...).  mode 0: statistics of the output; mode 1: backward sums of the GroupNorm `gn` (None =
         no group sums wanted).  `amax` (half-split mode): the input's magnitude rides in the same struct; the second
         return value is None when the launch leaves no group partials."""
         chunks = 0
-        if os.environ.get("FH_GN_EPILOGUE", "1") != "0" and Co % 32 == 0 and not (mode == 1 and gn is None):
+        if _switch("GN_EPILOGUE") and Co % 32 == 0 and not (mode == 1 and gn is None):
             chunks = self.lib.fh_conv2d_x6_gn_chunks(ks, N, H, W, Ci, Co, kh, kw, pad, 1)
         if chunks <= 0:
             if amax is None:
@@ -285,70 +306,52 @@ class HipOps:
         partial = torch.empty(N * chunks * 64, dtype=torch.float64, device=dev)
         e = _lib.FhGnEpilogue()
         e.partial, e.mode, e.act = partial.data_ptr(), mode, 0
-        e.in_amax = None if amax is None else amax.data_ptr()
+        e.in_amax = _ptr(amax)
         keep = [partial, chunks]
         if mode == 1:
             gn_name, x, stats, act, scale, shift = gn
             table = torch.empty(N, 5, Co, dtype=torch.float32, device=dev)
-            ss = 0 if scale is None else scale.stride(0)
-            _lib.check(self.lib.fh_groupnorm_bwd_table(
-                stats.data_ptr(), self.P[gn_name + ".weight"].data_ptr(), self.P[gn_name + ".bias"].data_ptr(),
-                None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss,
-                table.data_ptr(), N, Co, _lib.stream()), "gn_bwd_table")
+            _lib.check(self.lib.fh_groupnorm_bwd_table(stats.data_ptr(), *self._gn_operands(gn_name, scale, shift),
+                                                       table.data_ptr(), N, Co, _lib.stream()), "gn_bwd_table")
             e.x, e.tab, e.act = x.data_ptr(), table.data_ptr(), int(act)
             keep.append(table)
         return C.byref(e), keep
 
     def _gn_stats(self, x):
+        """(mean, rstd) [N][32][2] of x: from the block partials the producing convolution's epilogue left, else by a pass"""
         N, H, W, C_ = x.shape
+        stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
         pre = getattr(x, "_fh_gn", None)
-        if pre is not None:  # block partials left by the producing convolution's epilogue
-            stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
+        if pre is not None:
             _lib.check(self.lib.fh_groupnorm_finalize(pre[0].data_ptr(), stats.data_ptr(), N, pre[1],
                                                       float(H * W * (C_ // 32)), 0, _lib.stream()), "gn_finalize(0)")
             return stats
-        return self._gn_stats_pass(x)
-
-    def _gn_stats_pass(self, x):
-        N, H, W, C = x.shape
-        stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
         scratch = torch.empty(self.lib.fh_groupnorm_scratch_doubles(N, H * W), dtype=torch.float64, device=x.device)
-        _lib.check(self.lib.fh_groupnorm_stats(x.data_ptr(), stats.data_ptr(), scratch.data_ptr(), N, H * W, C,
+        _lib.check(self.lib.fh_groupnorm_stats(x.data_ptr(), stats.data_ptr(), scratch.data_ptr(), N, H * W, C_,
                                                _lib.stream()), "gn_stats")
         return stats
-
-    def _gn_apply(self, name, x, stats, act, scale=None, shift=None):
-        N, H, W, C = x.shape
-        y = torch.empty_like(x)
-        ss = 0 if scale is None else scale.stride(0)
-        _lib.check(self.lib.fh_groupnorm_apply(
-            x.data_ptr(), stats.data_ptr(), self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(),
-            None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss,
-            y.data_ptr(), N, H * W, C, int(act), _lib.stream()), "gn_apply")
-        return y
 
     def _gn_small(self, x):
         """whether the one-launch GroupNorm kernels take a tensor of x's shape (FH_GN_SMALL=0: the three-launch path)"""
         N, H, W, C_ = x.shape
-        return os.environ.get("FH_GN_SMALL", "1") != "0" and bool(self.lib.fh_groupnorm_small_supported(H * W, C_))
-
-    def _gn_fwd_small(self, name, x, act, scale=None, shift=None):
-        """statistics and result of a small GroupNorm in one launch (fh_groupnorm_fwd_small) -> (y, stats)"""
-        N, H, W, C_ = x.shape
-        y = torch.empty_like(x)
-        stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
-        ss = 0 if scale is None else scale.stride(0)
-        _lib.check(self.lib.fh_groupnorm_fwd_small(
-            x.data_ptr(), self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(),
-            None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss,
-            y.data_ptr(), stats.data_ptr(), N, H * W, C_, int(act), _lib.stream()), "gn_fwd_small")
-        return y, stats
+        return _switch("GN_SMALL") and bool(self.lib.fh_groupnorm_small_supported(H * W, C_))
 
     def _gn(self, name, x, act, scale=None, shift=None):
+        """act(GroupNorm(x) (1 + scale) + shift) -> (y, stats): one launch for a small tensor (fh_groupnorm_fwd_small) unless
+        its producer left group-sum partials; else the statistics (`_gn_stats`), then the apply pass"""
+        N, H, W, C_ = x.shape
+        gp = self._gn_operands(name, scale, shift)
         if getattr(x, "_fh_gn", None) is None and self._gn_small(x):
-            return self._gn_fwd_small(name, x, act, scale, shift)
+            y = torch.empty_like(x)
+            stats = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
+            _lib.check(self.lib.fh_groupnorm_fwd_small(x.data_ptr(), *gp, y.data_ptr(), stats.data_ptr(), N, H * W, C_,
+                                                       int(act), _lib.stream()), "gn_fwd_small")
+            return y, stats
         stats = self._gn_stats(x)
-        return self._gn_apply(name, x, stats, act, scale, shift), stats
+        y = torch.empty_like(x)
+        _lib.check(self.lib.fh_groupnorm_apply(x.data_ptr(), stats.data_ptr(), *gp, y.data_ptr(), N, H * W, C_, int(act),
+                                               _lib.stream()), "gn_apply")
+        return y, stats
 
     def _gn_conv(self, gn_name, conv_name, x, act, scale=None, shift=None, res=None):
         """conv3x3(act(GroupNorm(x))) - the in_layers / out_layers pattern of a ResBlock.  Where the row-reuse split-bf16
@@ -356,69 +359,50 @@ class HipOps:
         is never written.  Returns (conv output, GroupNorm statistics)."""
         c = self.conv[conv_name]
         N, H, W, Ci = x.shape
-        fuse = (c.wx_f is not None and c.kh == 3 and c.kw == 3 and Ci == c.ci_p and os.environ.get("FH_GN_FUSE", "1") != "0"
-                and self.lib.fh_conv2d_x6_norm_supported(N, H, W, Ci, c.co))
-        if not fuse and getattr(x, "_fh_gn", None) is None and self._gn_small(x):
-            y, stats = self._gn_fwd_small(gn_name, x, act, scale, shift)
+        if not (c.wx_f is not None and c.kh == 3 and c.kw == 3 and Ci == c.ci_p and _switch("GN_FUSE")
+                and self.lib.fh_conv2d_x6_norm_supported(N, H, W, Ci, c.co)):
+            y, stats = self._gn(gn_name, x, act, scale, shift)
             return self._conv(conv_name, y, res=res), stats
         stats = self._gn_stats(x)
-        if fuse:
-            table = torch.empty(N, 2, Ci, dtype=torch.float32, device=x.device)
-            ss = 0 if scale is None else scale.stride(0)
-            _lib.check(self.lib.fh_groupnorm_table(
-                stats.data_ptr(), self.P[gn_name + ".weight"].data_ptr(), self.P[gn_name + ".bias"].data_ptr(),
-                None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss,
-                table.data_ptr(), N, Ci, _lib.stream()), "gn_table")
-            out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
-            epi, keep = self._epilogue(1, N, H, W, Ci, c.co, 3, 3, 1, 0)
-            _lib.check(self.lib.fh_conv2d_x6_norm_nhwc_gn(x.data_ptr(), table.data_ptr(), int(act),
-                                                          c.planes(True, self._launch_mode(c)).data_ptr(),
-                                                          c.b.data_ptr(), None if res is None else res.data_ptr(),
-                                                          out.data_ptr(), N, H, W, Ci, c.co, epi, _lib.stream()),
-                       "fh_conv2d_x6_norm_nhwc")
-            if keep is not None:
-                out._fh_gn = keep
-            return out, stats
-        return self._conv(conv_name, self._gn_apply(gn_name, x, stats, act, scale, shift), res=res), stats
+        table = torch.empty(N, 2, Ci, dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.fh_groupnorm_table(stats.data_ptr(), *self._gn_operands(gn_name, scale, shift), table.data_ptr(),
+                                               N, Ci, _lib.stream()), "gn_table")
+        out = torch.empty(N, H, W, c.co, dtype=torch.float32, device=x.device)
+        epi, keep = self._epilogue(1, N, H, W, Ci, c.co, 3, 3, 1, 0)
+        _lib.check(self.lib.fh_conv2d_x6_norm_nhwc_gn(x.data_ptr(), table.data_ptr(), int(act),
+                                                      c.planes(True, self._launch_mode(c)).data_ptr(), c.b.data_ptr(),
+                                                      _ptr(res), out.data_ptr(), N, H, W, Ci, c.co, epi, _lib.stream()),
+                   "fh_conv2d_x6_norm_nhwc")
+        if keep is not None:
+            out._fh_gn = keep
+        return out, stats
 
     def _gn_bwd(self, name, x, stats, dy, act, scale=None, shift=None, accumulate_into=None, add2=None, split=None):
         """dL/dx of GroupNorm(+scale-shift)(+SiLU) given dL/dy.  `accumulate_into`: the gradient arriving over the block's
         skip path is added (in place unless `split`); `add2`: one more addend (the gradient of a U-Net skip tensor forked at
         this point); `split` = (Ca, Cb): the result is returned as two tensors [.., Ca], [.., Cb] (x was a channel concat)."""
         N, H, W, C_ = x.shape
-        ss = 0 if scale is None else scale.stride(0)
-        gp = (self.P[name + ".weight"].data_ptr(), self.P[name + ".bias"].data_ptr(),
-              None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(), ss)
-        sums = getattr(dy, "_fh_gn_sums", None)  # left by the producing input-gradient convolution's epilogue
-        if sums is None and self.bf16 != 4 and self._gn_small(x):  # sums and result in one launch
-            acc = accumulate_into
-            if split is not None:
-                dx = torch.empty(N, H, W, split[0], dtype=torch.float32, device=x.device)
-                dx2 = torch.empty(N, H, W, split[1], dtype=torch.float32, device=x.device)
-            else:
-                dx, dx2 = (acc if acc is not None else torch.empty_like(x)), None
-            _lib.check(self.lib.fh_groupnorm_bwd_small(
-                x.data_ptr(), dy.data_ptr(), stats.data_ptr(), None, *gp, None if acc is None else acc.data_ptr(),
-                None if add2 is None else add2.data_ptr(), dx.data_ptr(), None if dx2 is None else dx2.data_ptr(),
-                0 if split is None else split[0], N, H * W, C_, int(act), _lib.stream()), "gn_bwd_small")
-            return dx if split is None else (dx, dx2)
-        if sums is None:
-            sums = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
-            scratch = torch.empty(self.lib.fh_groupnorm_scratch_doubles(N, H * W), dtype=torch.float64, device=x.device)
-            _lib.check(self.lib.fh_groupnorm_bwd_sums(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), *gp, sums.data_ptr(),
-                                                      scratch.data_ptr(), N, H * W, C_, int(act), _lib.stream()), "gn_bwd_sums")
         acc = accumulate_into
         if split is not None:
             dx = torch.empty(N, H, W, split[0], dtype=torch.float32, device=x.device)
             dx2 = torch.empty(N, H, W, split[1], dtype=torch.float32, device=x.device)
         else:
             dx, dx2 = (acc if acc is not None else torch.empty_like(x)), None
+        gp = self._gn_operands(name, scale, shift)
+        tail = (_ptr(acc), _ptr(add2), dx.data_ptr(), _ptr(dx2), 0 if split is None else split[0], N, H * W, C_, int(act))
+        sums = getattr(dy, "_fh_gn_sums", None)  # left by the producing input-gradient convolution's epilogue
+        if sums is None and self.bf16 != 4 and self._gn_small(x):  # sums and result in one launch
+            _lib.check(self.lib.fh_groupnorm_bwd_small(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), None, *gp, *tail,
+                                                       _lib.stream()), "gn_bwd_small")
+            return dx if split is None else (dx, dx2)
+        if sums is None:
+            sums = torch.empty(N, 32, 2, dtype=torch.float32, device=x.device)
+            scratch = torch.empty(self.lib.fh_groupnorm_scratch_doubles(N, H * W), dtype=torch.float64, device=x.device)
+            _lib.check(self.lib.fh_groupnorm_bwd_sums(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), *gp, sums.data_ptr(),
+                                                      scratch.data_ptr(), N, H * W, C_, int(act), _lib.stream()), "gn_bwd_sums")
         amax = self._amax_slot() if self.bf16 == 4 else None  # the magnitudes of dx, dx2 for the half-split dgrad that follows
-        _lib.check(self.lib.fh_groupnorm_bwd_apply_ex(
-            x.data_ptr(), dy.data_ptr(), stats.data_ptr(), sums.data_ptr(), *gp, None if acc is None else acc.data_ptr(),
-            None if add2 is None else add2.data_ptr(), dx.data_ptr(), None if dx2 is None else dx2.data_ptr(),
-            0 if split is None else split[0], N, H * W, C_, int(act), None if amax is None else amax.data_ptr(),
-            _lib.stream()), "gn_bwd_apply")
+        _lib.check(self.lib.fh_groupnorm_bwd_apply_ex(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), sums.data_ptr(), *gp,
+                                                      *tail, _ptr(amax), _lib.stream()), "gn_bwd_apply")
         if amax is not None:
             dx._fh_amax = amax[0]
             if dx2 is not None:
@@ -512,7 +496,7 @@ class HipOps:
         T = H * W
         hn, st = self._gn(p + ".norm", x, act=0)
         qkv = self._conv(p + ".qkv", hn)  # [N,H,W,3C]
-        if (os.environ.get("FH_ATTN_FUSED", "1") != "0" and self.lib.fh_attention_supported(T, C, heads)
+        if (_switch("ATTN_FUSED") and self.lib.fh_attention_supported(T, C, heads)
                 and N * heads <= 65535):  # (image, head) pairs ride in gridDim.y
             # one kernel: q k^T -> online softmax -> . v; the tape keeps the output and the log-sum-exp, not the weights
             A = torch.empty(N, H, W, C, dtype=torch.float32, device=x.device)
@@ -634,7 +618,7 @@ class HipOps:
         recs = list(reversed(tape))
         presplit = None   # (ga, gb) when the block before a pop_cat already wrote the concat's gradient as two tensors
         skip_push = False
-        fold = os.environ.get("FH_GLUE_FOLD", "1") != "0"
+        fold = _switch("GLUE_FOLD")
         for ri, rec in enumerate(recs):
             kind = rec[0]
             nxt = recs[ri + 1] if ri + 1 < len(recs) else (None,)

@@ -325,8 +325,6 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* shared, const fh_batc
 int fh_conv2d_nhwc(const float* in, const float* w, const float* bias, const float* res, float* out, float* ws,
                    int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
                    void* stream);
-/* recommended K-split for a layer (1 = none).  With ksplit > 1 the K range is divided over blockIdx.z, raw partial
- * sums go to ws [ksplit][N*Ho*Wo][Cout] (caller-owned) and a second kernel adds them in a fixed order (+ bias, res). */
 /* Precision of the convolution kernels that run on the bf16 matrix cores (fh_conv2d_x6_nhwc, fh_conv2d_x6_norm_nhwc):
  * 0 (default) = exact 3-way operand split, fp32 accuracy; 1 = plain bf16 compute (operands rounded to bf16, one product,
  * fp32 accumulation) - the reduced-precision UNet mode, counterpart of the reference's fp16 torso
@@ -349,6 +347,8 @@ int fh_unet_get_precision(void);
  * activation operand by.  FH_AMAX_SLOTS partial maxima instead of one value because same-address atomics serialise. */
 #define FH_AMAX_SLOTS 16
 int fh_absmax_f32(const float* x, int64_t n, float* out, void* stream);
+/* recommended K-split for a layer (1 = none).  With ksplit > 1 the K range is divided over blockIdx.z, raw partial
+ * sums go to ws [ksplit][N*Ho*Wo][Cout] (caller-owned) and a second kernel adds them in a fixed order (+ bias, res). */
 int fh_conv2d_splitk(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW);
 
 /* Same convolution as fh_conv2d_nhwc at fp32 accuracy on the bf16 matrix cores: operands are split exactly into three

@@ -20,10 +20,10 @@ def wrap(name, keyfn, flopfn=None):
 wrap("_conv", lambda s,n,x,**k:(tuple(x.shape), s.conv[n].co, s.conv[n].kh), lambda s,n,x,**k: 2.0*x.shape[0]*x.shape[1]*x.shape[2]*x.shape[3]*s.conv[n].co*s.conv[n].kh*s.conv[n].kw)
 wrap("_dgrad", lambda s,n,g,**k:(tuple(g.shape), s.conv[n].ci, s.conv[n].kh), lambda s,n,g,**k: 2.0*g.shape[0]*g.shape[1]*g.shape[2]*s.conv[n].co_p*s.conv[n].ci*s.conv[n].kh*s.conv[n].kw)
 wrap("_gn_stats", lambda s,x:(tuple(x.shape),))
-wrap("_gn_apply", lambda s,n,x,*a,**k:(tuple(x.shape),))
+wrap("_gn", lambda s,n,x,*a,**k:(tuple(x.shape),))
 wrap("_gn_conv", lambda s,g,c,x,*a,**k:(tuple(x.shape), s.conv[c].co), lambda s,g,c,x,*a,**k: 2.0*x.shape[0]*x.shape[1]*x.shape[2]*x.shape[3]*s.conv[c].co*9)
 wrap("_attn_fwd", lambda s,p,x,h,t:(tuple(x.shape),))
-wrap("_attn_bwd", lambda s,rec,g:(tuple(g.shape),))
+wrap("_attn_bwd", lambda s,rec,g,**k:(tuple(g.shape),))
 wrap("_gn_bwd", lambda s,n,x,st,dy,act,*a,**k:(tuple(x.shape),))
 wrap("_resample", lambda s,x,m:(tuple(x.shape),m))
 wrap("_add", lambda s,a,b:(tuple(a.shape),))
