@@ -209,7 +209,37 @@ struct ConvArgsX {
   // magnitude (in_amax, device) or, for the fused-GroupNorm input, the fixed in_scale
   const float* in_amax;
   float in_scale;
+  int wide;  // k_conv_x6r with TT: 1 = Cout % 4 == 0 and out / res / gn_x 16-byte aligned, the epilogue moves float4 per lane
+#ifdef FH_CONV_PHASE_CLOCKS
+  unsigned long long* phase;  // [flat workgroup id][8] or null
+#endif
 };
+
+// Phase clocks of the LDS-DMA 256-pixel tile, in the diagnostic build of profiles/tools/conv_tile_phases.py only (the shipped
+// library has no stamp): thread 0 of the workgroup leaves s_memtime at 0 entry, 1 first barrier passed, 2 K loop done, 3 last
+// store issued, 4 group sums reduced and stores retired (exit), and HW_ID / XCC_ID in 5 / 6, in the row of its workgroup id.
+#ifdef FH_CONV_PHASE_CLOCKS
+#define FH_PHASE(slot, k)                                                                                       \
+  do {                                                                                                          \
+    if (threadIdx.x == 0 && a.phase != nullptr) a.phase[(size_t)(slot) * 8 + (k)] = __builtin_amdgcn_s_memtime(); \
+  } while (0)
+#define FH_PHASE_EXIT(slot)                                                                     \
+  do {                                                                                          \
+    __builtin_amdgcn_s_waitcnt(0);                                                              \
+    FH_PHASE(slot, 4);                                                                          \
+    if (threadIdx.x == 0 && a.phase != nullptr) {                                               \
+      a.phase[(size_t)(slot) * 8 + 5] = (1ull << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4); /* HW_ID */ \
+      a.phase[(size_t)(slot) * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20); /* XCC_ID */ \
+    }                                                                                           \
+  } while (0)
+#else
+#define FH_PHASE(slot, k) \
+  do {                    \
+  } while (0)
+#define FH_PHASE_EXIT(slot) \
+  do {                      \
+  } while (0)
+#endif
 
 // SiLU with the hardware reciprocal (1 ulp) instead of an IEEE division (~10 instructions): the fused-input convolution
 // evaluates it while staging its activation tile, where every VALU cycle is exposed; the stand-alone apply kernel uses the
@@ -224,12 +254,12 @@ __device__ __forceinline__ float silu_f(float v) { return v * __builtin_amdgcn_r
 struct GnAcc {  // per lane: <= 32 values of one channel, summed in fp32 (then widened for the cross-lane / cross-tile sums)
   float s0, s1;
 };
-__device__ __forceinline__ void gn_accum(const ConvArgsX& a, GnAcc& g, float v, int64_t row, int co, const float (&tb)[5]) {
+// (x: the element of gn_x at v's position, read only in mode 1)
+__device__ __forceinline__ void gn_accum_x(const ConvArgsX& a, GnAcc& g, float v, float x, const float (&tb)[5]) {
   if (a.gn_mode == 0) {
     g.s0 += v;
     g.s1 = fmaf(v, v, g.s1);
   } else {
-    const float x = a.gn_x[row * a.Cout + co];
     const float t = fmaf(x, tb[0], tb[1]);
     const float xh = (x - tb[2]) * tb[3];
     float gg = v;
@@ -241,6 +271,27 @@ __device__ __forceinline__ void gn_accum(const ConvArgsX& a, GnAcc& g, float v, 
     g.s0 += gg;
     g.s1 = fmaf(gg, xh, g.s1);
   }
+}
+__device__ __forceinline__ void gn_accum(const ConvArgsX& a, GnAcc& g, float v, int64_t row, int co, const float (&tb)[5]) {
+  gn_accum_x(a, g, v, a.gn_mode == 0 ? 0.f : a.gn_x[row * a.Cout + co], tb);
+}
+
+// 4 x 4 transpose inside every lane quad (DPP quad_perm): lane k of a quad gives t[q] and receives lane q's t[k].  In the
+// 32 x 32 accumulator layout a lane holds four consecutive rows of one channel per register group and the quad four
+// adjacent channels, so afterwards a lane holds four adjacent channels of one row: one 16-byte access.  An involution.
+template <int X>
+__device__ __forceinline__ void quad_swap(float& lo, float& hi, bool up) {
+  const float send = up ? lo : hi;
+  const float recv = __builtin_bit_cast(
+      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), X == 1 ? 0xB1 : 0x4E, 0xF, 0xF, true));
+  lo = up ? recv : lo;
+  hi = up ? hi : recv;
+}
+__device__ __forceinline__ void quad_transpose(float (&t)[4], int k) {
+  quad_swap<1>(t[0], t[1], (k & 1) != 0);
+  quad_swap<1>(t[2], t[3], (k & 1) != 0);
+  quad_swap<2>(t[0], t[2], (k & 2) != 0);
+  quad_swap<2>(t[1], t[3], (k & 2) != 0);
 }
 template <int NI, int WM, int WN, int BN>
 __device__ __forceinline__ void gn_reduce(const ConvArgsX& a, const GnAcc (&g)[NI], double* gred, int n, int chunk, int n0) {
@@ -566,9 +617,15 @@ __global__ __launch_bounds__(64 * WM * WN, MINW) void k_conv_x6(ConvArgsX a) {
 // range may start or end inside a kernel row: the row of (cc, ky) of c_begin is staged whatever its kx, and restaged whenever
 // kx returns to 0.  Per accumulator element the MFMAs, their operands and their order are those of k_conv_x6 (chunk order
 // (cc, ky, kx), halo and padding pixels exact zeros like its masked loads), so the two kernels agree to the last bit.
-template <int SEGW, bool NORM = false, int BM = 128, int NP = 3, int GL = 0, bool F16 = false, bool SPLIT = false>  // SEGW: pixels per row segment of the tile (W, capped at BM)
+// TT (tile tail, the exact-split 256-pixel LDS-DMA tile only; FH_CONV_TILE_TAIL=0 launches TT = false, the form above): the
+// epilogue moves 16 bytes per lane.  A 4 x 4 transpose in every lane quad turns the 32 dword stores of a wave into 8 dwordx4
+// stores; `res` and `gn_x` arrive as float4 and are transposed BACK into the accumulator layout, where v and the group sums
+// are formed exactly as before (same values, same order per lane), then v is transposed and stored.  The dword loads of
+// `res` / `gn_x` were a quarter of such a tile's time (profiles/conv_tile_tail.md); the plain store tail gains nothing.
+template <int SEGW, bool NORM = false, int BM = 128, int NP = 3, int GL = 0, bool F16 = false, bool SPLIT = false, bool TT = false>  // SEGW: pixels per row segment of the tile (W, capped at BM)
 __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
   static_assert(!SPLIT || (GL == 0 && BM == 128 && !NORM), "split-K: the register-staged 128-pixel tile, plain input");
+  static_assert(!TT || (GL == 1 && BM == 256 && NP == 3 && !F16 && !SPLIT), "tile tail: the exact-split 256-pixel tile");
   constexpr int MI = 2, NI = 1, WN = 4, T = 4 * BM;
   constexpr int NSEG = BM / SEGW, SP = SEGW + 2;  // row segments per tile, staged pixels per segment (one halo each side)
   constexpr int BN = 128, AR = NSEG * SP;
@@ -589,6 +646,9 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave / WN) * (MI * 32), wn = (wave % WN) * (NI * 32);
   const int lr = lane & 31, lh = lane >> 5;
+  const unsigned flat_id = blockIdx.y * gridDim.x + blockIdx.x;
+  (void)flat_id;
+  if (GL == 1) FH_PHASE(flat_id, 0);
   int tile_m, tile_n;
   xcd_tile(tile_m, tile_n);
   const int64_t m0 = (int64_t)tile_m * BM;
@@ -829,6 +889,7 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
     issue_b(0, 0, 0);
     store_a();
     __syncthreads();  // (the barrier's fence also retires the DMA)
+    FH_PHASE(flat_id, 1);
     for (int c = 0; c < nchunks; ++c) {
       const int kx = c % 3, nx = c + 1;
       const bool more = nx < nchunks, new_row = more && (nx % 3 == 0);
@@ -844,6 +905,7 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
         __syncthreads();
       }
     }
+    FH_PHASE(flat_id, 2);
   } else if (!SPLIT || c_begin < c_end) {  // (a split-K slice of a short K range may be empty: its slab is zeros)
   load_a(c_begin / 9, (c_begin / 3) % 3);
   load_b(c_begin / 9, c_begin % 9);
@@ -886,6 +948,39 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
 #pragma unroll
       for (int q = 0; q < 5; ++q) tb[q] = a.gn_tab[((int64_t)pn * 5 + q) * a.Cout + co];
     }
+    if (TT && a.wide) {
+      // (Cout % 4 == 0: a lane quad's four channels are inside Cout together; M % BM == 0: every row is inside M)
+      const int k = lane & 3;
+      const bool has_res = a.res != nullptr, has_x = gn && a.gn_mode == 1;
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        float4 rw[4], xw[4];
+        const int64_t off0 = (m0 + wm + i * 32 + 4 * lh + k) * a.Cout + (co - k);  // this lane's row and channel quad
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int64_t off = off0 + (int64_t)(8 * g) * a.Cout;
+          rw[g] = has_res ? *reinterpret_cast<const float4*>(a.res + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+          xw[g] = has_x ? *reinterpret_cast<const float4*>(a.gn_x + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float r4[4] = {rw[g].x, rw[g].y, rw[g].z, rw[g].w}, x4[4] = {xw[g].x, xw[g].y, xw[g].z, xw[g].w}, v4[4];
+          if (has_res) quad_transpose(r4, k);
+          if (has_x) quad_transpose(x4, k);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {  // accumulator register 4 g + q: row 8 g + 4 lh + q, the order of the 4-byte form
+            float v = acc[i][j][4 * g + q];
+            v += bv;
+            if (has_res) v += r4[q];
+            v4[q] = v;
+            if (gn) gn_accum_x(a, gsum[j], v, x4[q], tb);
+          }
+          quad_transpose(v4, k);
+          *reinterpret_cast<float4*>(dst + off0 + (int64_t)(8 * g) * a.Cout) = make_float4(v4[0], v4[1], v4[2], v4[3]);
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -902,7 +997,9 @@ __global__ __launch_bounds__(4 * BM, 4) void k_conv_x6r(ConvArgsX a) {
       }
     }
   }
+  if (GL == 1) FH_PHASE(flat_id, 3);
   if (gn) gn_reduce<NI, BM / 64, WN, BN>(a, gsum, gred, pn, (rem / BM) * (int)gridDim.y + tile_n, n0);
+  if (GL == 1) FH_PHASE_EXIT(flat_id);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1992,6 +2089,12 @@ X6Plan x6_plan(int ksplit, int N, int H, int W, int /*Cin: no tile depends on it
   return p;
 }
 
+// FH_CONV_TILE_TAIL=0 launches the exact-split 256-pixel tiles with the 4-byte epilogue (A/B switch, read once per process)
+bool conv_tile_tail_enabled() {
+  static const bool on = !(getenv("FH_CONV_TILE_TAIL") != nullptr && atoi(getenv("FH_CONV_TILE_TAIL")) == 0);
+  return on;
+}
+
 // the five precision instantiations of one tile (fh_unet_set_precision)
 template <int SEGW, bool NORM, int BM, int GL, bool SPLIT = false>
 void launch_x6r(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
@@ -2018,13 +2121,22 @@ void launch_x6(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
 
 constexpr int tile_key(int bm, int w, int gl = 0) { return (bm * 1024 + w) * 2 + gl; }
 
+// The 256-pixel LDS-DMA tile: in the exact-split default its epilogue moves 16 bytes per lane (same grid, same bits)
+template <int SEGW, bool NORM>
+void launch_x6r_256(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
+  if (g_conv_np == 3 && conv_tile_tail_enabled())
+    hipLaunchKernelGGL((k_conv_x6r<SEGW, NORM, 256, 3, 1, false, false, true>), p.grid, p.block, 0, st, a);
+  else
+    launch_x6r<SEGW, NORM, 256, 1>(p, st, a);
+}
+
 // one switch over the row-reuse combinations (BM, SEGW, GL); false for a plan no kernel is built for
 template <bool NORM>
 bool launch_x6r_tile(const X6Plan& p, hipStream_t st, const ConvArgsX& a) {
   switch (tile_key(p.bm, p.segw, p.gl)) {
-    case tile_key(256, 256, 1): launch_x6r<256, NORM, 256, 1>(p, st, a); return true;
-    case tile_key(256, 128, 1): launch_x6r<128, NORM, 256, 1>(p, st, a); return true;
-    case tile_key(256, 64, 1): launch_x6r<64, NORM, 256, 1>(p, st, a); return true;
+    case tile_key(256, 256, 1): launch_x6r_256<256, NORM>(p, st, a); return true;
+    case tile_key(256, 128, 1): launch_x6r_256<128, NORM>(p, st, a); return true;
+    case tile_key(256, 64, 1): launch_x6r_256<64, NORM>(p, st, a); return true;
     case tile_key(128, 128, 0): launch_x6r<128, NORM, 128, 0>(p, st, a); return true;
     case tile_key(128, 64, 0): launch_x6r<64, NORM, 128, 0>(p, st, a); return true;
     case tile_key(128, 32, 0): launch_x6r<32, NORM, 128, 0>(p, st, a); return true;
@@ -2148,6 +2260,15 @@ int fh_conv2d_x6_plan(int ksplit, int N, int H, int W, int Cin, int Cout, int KH
   return 0;
 }
 
+#ifdef FH_CONV_PHASE_CLOCKS
+static unsigned long long* g_phase_buf = nullptr;
+// diagnostic build only: device buffer [planned workgroups][8] of uint64 that the next 256-pixel launches stamp, or null
+int fh_conv_phase_buffer(void* buf) {
+  g_phase_buf = (unsigned long long*)buf;
+  return 0;
+}
+#endif
+
 static int set_gn(ConvArgsX& a, const fh_gn_epilogue* epi, int chunks) {
   a.gn_partial = nullptr, a.gn_x = nullptr, a.gn_tab = nullptr, a.gn_mode = a.gn_act = a.gn_chunks = 0;
   a.in_amax = epi != nullptr ? epi->in_amax : nullptr, a.in_scale = 1.f;
@@ -2181,6 +2302,10 @@ static int conv2d_x6_launch(const float* in, bool norm, const float* ab_table, i
     const int rc = set_gn(a, epi, p.gn_bm ? (a.Ho * a.Wo / p.gn_bm) * ((Cout + 127) / 128) : 0);
     if (rc) return rc;
   }
+#ifdef FH_CONV_PHASE_CLOCKS
+  a.phase = g_phase_buf;
+#endif
+  a.wide = Cout % 4 == 0 && (((uintptr_t)out | (uintptr_t)res | (uintptr_t)a.gn_x) & 15) == 0;
   hipStream_t st = (hipStream_t)stream;
   const bool built = !p.reuse ? launch_x6_tile(p, st, a)
                      : p.split ? launch_x6r_split_tile(p, st, a)

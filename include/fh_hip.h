@@ -398,6 +398,10 @@ int fh_conv2d_x6_gn_chunks(int ksplit, int N, int H, int W, int Cin, int Cout, i
  * the same bits. */
 int fh_conv2d_x6_plan(int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
                       int32_t* plan);
+/* The exact-split 256-pixel tiles (plan[1] == 256, precision mode 0) move 16 bytes per lane in their epilogue (output,
+ * residual and the group-sum epilogue's x) where Cout % 4 == 0 and the three pointers are 16-byte aligned.
+ * FH_CONV_TILE_TAIL=0 in the environment (read once per process) launches the kernel with the 4-byte epilogue instead; both
+ * write the same bits, the plan and the partial layout do not change. */
 int fh_conv2d_x6_nhwc_gn(const float* in, const void* wx, const float* bias, const float* res, float* out, float* ws,
                          int ksplit, int N, int H, int W, int Cin, int Cout, int KH, int KW, int pad, int stride,
                          const fh_gn_epilogue* epi, void* stream);

@@ -7,6 +7,9 @@
         with events on the stream, REPEATS repeats of LAUNCHES launches.  The generic kernel (switch off) runs first AND
         last; its spread per shape is max - min over the repeats of both runs, and a gain counts where the medians differ by
         more than that.  --parent-root: another checkout (built) whose library is timed as well.
+    bench_x6.py --tile-tail [--batches 4,8] [--parent-root DIR] [--out FILE.json]
+        A/B of the 16-byte epilogue of the 256-pixel tiles (switch FH_CONV_TILE_TAIL) on five launches of the 256^2 and
+        128^2 levels - plain, residual + group sums, backward group sums, fused GroupNorm input - by the same method.
 """
 import json, os, statistics, subprocess, sys
 ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -104,6 +107,93 @@ def splitk_main(argv):
         json.dump({"shapes": shapes, "repeats": REPEATS, "launches": LAUNCHES, "us_per_call": res}, open(opt["--out"], "w"))
 
 
+TAIL_SHAPES = [(256, 256, 128, 128, "plain"), (256, 256, 128, 128, "res_gn0"), (256, 256, 128, 128, "gn1"),
+               (256, 256, 256, 128, "norm"), (128, 128, 256, 256, "plain")]
+
+
+def tail_child(root, batches):
+    """times the five 256-pixel-tile launches of --tile-tail with the library of checkout `root`"""
+    import ctypes
+    sys.path.insert(0, root)
+    import torch
+    from free_hunch_amd import _lib as L
+    lib = L.load(); dev = torch.device('cuda:0'); out = {}
+    for N in [int(v) for v in batches.split(",")]:
+        for (H, W, Ci, Co, mode) in TAIL_SHAPES:
+            g = torch.Generator().manual_seed(N + H + Ci + Co)
+            x = torch.randn(N, H, W, Ci, generator=g).to(dev)
+            wd = (torch.randn(Co, 9, Ci, generator=g) * 0.03).to(dev)
+            h = wd.to(torch.bfloat16); r = wd - h.float(); m = r.to(torch.bfloat16); l = (r - m.float()).to(torch.bfloat16)
+            wx = torch.stack([h, m, l]).reshape(3, Co, 9, Ci // 32, 32).permute(0, 2, 3, 1, 4).contiguous()
+            b = torch.zeros(Co, device=dev); o = torch.empty(N, H, W, Co, device=dev)
+            res = torch.randn(N, H, W, Co, generator=g).to(dev) if mode == "res_gn0" else None
+            chunks = lib.fh_conv2d_x6_gn_chunks(1, N, H, W, Ci, Co, 3, 3, 1, 1)
+            partial = torch.zeros(N * chunks * 64, dtype=torch.float64, device=dev)
+            e = L.FhGnEpilogue(); e.partial, e.mode, e.act = partial.data_ptr(), int(mode == "gn1"), 1
+            if mode == "gn1":
+                xin = torch.randn(N, H, W, Co, generator=g).to(dev); tab = torch.randn(N, 5, Co, generator=g).to(dev)
+                e.x, e.tab = xin.data_ptr(), tab.data_ptr()
+            table = torch.cat([1 + 0.1 * torch.randn(N, 1, Ci, generator=g), 0.1 * torch.randn(N, 1, Ci, generator=g)], 1).to(dev).contiguous()
+            rp = res.data_ptr() if res is not None else None
+            if mode == "plain":
+                f = lambda: L.check(lib.fh_conv2d_x6_nhwc(x.data_ptr(), wx.data_ptr(), b.data_ptr(), None, o.data_ptr(), None, 1,
+                                                          N, H, W, Ci, Co, 3, 3, 1, 1, L.stream()), "x6")
+            elif mode == "norm":
+                f = lambda: L.check(lib.fh_conv2d_x6_norm_nhwc(x.data_ptr(), table.data_ptr(), 1, wx.data_ptr(), b.data_ptr(), None,
+                                                               o.data_ptr(), N, H, W, Ci, Co, L.stream()), "x6 norm")
+            else:
+                f = lambda: L.check(lib.fh_conv2d_x6_nhwc_gn(x.data_ptr(), wx.data_ptr(), b.data_ptr(), rp, o.data_ptr(), None, 1,
+                                                             N, H, W, Ci, Co, 3, 3, 1, 1, ctypes.byref(e), L.stream()), "x6 gn")
+            for _ in range(10): f()
+            ts = []
+            for _ in range(REPEATS):
+                torch.cuda.synchronize(); e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(LAUNCHES): f()
+                e1.record(); torch.cuda.synchronize(); ts.append(1e3 * e0.elapsed_time(e1) / LAUNCHES)
+            out["%d,%d,%d,%d,%d,%s" % (N, H, W, Ci, Co, mode)] = ts
+    print("RESULT " + json.dumps(out), flush=True)
+
+
+def tail_main(argv):
+    """--tile-tail [--batches 4,8] [--parent-root DIR] [--out FILE.json]: A/B of the 16-byte epilogue of the 256-pixel tiles.
+    The parent form (the library of --parent-root, else this one with FH_CONV_TILE_TAIL=0) runs first and last, between them
+    this library with the switch off (the 4-byte epilogue it keeps) and with the default; every variant is a child process.
+    Spread = max - min of the parent form's 2 x REPEATS repeats; * marks a gain beyond it."""
+    opt = {argv[i]: argv[i + 1] for i in range(len(argv) - 1) if argv[i].startswith("--")}
+    batches = opt.get("--batches", "4,8")
+    proot = os.path.abspath(opt["--parent-root"]) if "--parent-root" in opt else ROOT
+    variants = [("parent_first", proot, {"FH_CONV_TILE_TAIL": "0"}), ("switch_off", ROOT, {"FH_CONV_TILE_TAIL": "0"}),
+                ("epilogue16", ROOT, {}), ("parent_last", proot, {"FH_CONV_TILE_TAIL": "0"})]
+    res = {}
+    for name, root, env in variants:
+        e = dict(os.environ, **env)
+        if not env:
+            e.pop("FH_CONV_TILE_TAIL", None)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--tile-tail-child", root, batches], env=e,
+                           stdout=subprocess.PIPE, text=True, timeout=600, check=True)
+        res[name] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        print("ran", name, flush=True)
+    print("us per launch, median of %d x %d launches; spread = max - min of the parent form's %d repeats" % (REPEATS, LAUNCHES, 2 * REPEATS))
+    print("| N | H x W | Cin | Cout | mode | parent | spread | switch off | gain | 16-byte epilogue | gain |")
+    print("|---" * 11 + "|")
+    for key in res["parent_first"]:
+        par = res["parent_first"][key] + res["parent_last"][key]
+        pm, sp = statistics.median(par), max(par) - min(par)
+        cells = []
+        for n in ("switch_off", "epilogue16"):
+            m = statistics.median(res[n][key])
+            cells.append("%.1f | %+.1f (%+.1f %%)%s" % (m, pm - m, 100 * (pm - m) / pm, " *" if pm - m > sp else ""))
+        N, H, W, Ci, Co, mode = key.split(",")
+        print("| %s | %s x %s | %s | %s | %s | %.1f | %.1f | %s |" % (N, H, W, Ci, Co, mode, pm, sp, " | ".join(cells)))
+    if "--out" in opt:
+        json.dump({"repeats": REPEATS, "launches": LAUNCHES, "us_per_launch": res}, open(opt["--out"], "w"))
+
+
+if "--tile-tail-child" in sys.argv:
+    tail_child(*sys.argv[sys.argv.index("--tile-tail-child") + 1:][:2]); sys.exit(0)
+if "--tile-tail" in sys.argv:
+    tail_main(sys.argv[1:]); sys.exit(0)
 if "--splitk-child" in sys.argv:
     splitk_child(*sys.argv[sys.argv.index("--splitk-child") + 1:][:2]); sys.exit(0)
 if "--splitk" in sys.argv:
