@@ -63,12 +63,13 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 
 
 # fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
-# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, see _problem)
+# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, see _problem)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
-            "noise": 0}
+            "noise": 0, "masked_blur": 5}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
+_SHARED_PSF = ("custom_blur", "masked_blur")  # operators whose PSF is the caller's: a lock-step batch must share it
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', 'noise', or 'custom_blur'.")
+                 "'colorization', 'noise', 'custom_blur', or 'masked_blur'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -95,13 +96,14 @@ def _problem(operator, cov, sigma_y2):
         mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
         p.mask = mask.data_ptr()
         keep.append(mask)
-    elif operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
+        return p, keep
+    if operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
         p.ntaps, p.tap_w = 3, w.data_ptr()
         keep.append(w)
-    elif p.op == 1 and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
+    elif p.op in (1, 5) and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
         win, hy, hx = operator.taps.window
-        p.op, p.ntaps, p.halo, p.tap_w = 4, win.numel(), 64 * hy + hx, win.data_ptr()
+        p.op, p.ntaps, p.halo, p.tap_w = (4 if p.op == 1 else 6), win.numel(), 64 * hy + hx, win.data_ptr()
         keep.append(win)
     else:
         t = operator.taps
@@ -111,12 +113,16 @@ def _problem(operator, cov, sigma_y2):
             p.tap2_dy, p.tap2_dx, p.tap2_w = t2.dy.data_ptr(), t2.dx.data_ptr(), t2.w.data_ptr()
         p.ntaps, p.halo = t.n, t.halo
         p.tap_dy, p.tap_dx, p.tap_w = t.dy.data_ptr(), t.dx.data_ptr(), t.w.data_ptr()
-        fold = operator.folded_bases() if (cov.use_dct and p.op == 1) else None
+        fold = operator.folded_bases() if (cov.use_dct and p.op in (1, 5)) else None
         if fold is not None:  # separable blur absorbed by the DCT passes of A C A^T (measurements.folded_dct_blur_bases)
             mats, sym = fold
             p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in mats)
             p.fold_sym = int(sym)
             keep.extend(mats)
+    if operator.name == "masked_blur":  # A = M B: the mask rides with the blur's fields (ops 5 / 6); kept LAST in `keep`
+        mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
+        p.mask = mask.data_ptr()
+        keep.append(mask)
     return p, keep
 
 
@@ -154,6 +160,8 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     else:
         ax = operator._conv(x64, stride=prob.stride)
         b = ctx.axpby(1.0, y64, -1.0, ax, ax)
+        if name == "masked_blur":  # b = M (y - B x0)
+            b = (keep[-1].view_as(b) * b).contiguous()
     sol = torch.empty_like(b)
     info = _lib.FhCgInfo()
     rtol = rtol_func(sigma_t, max_rtol) if rtol is None else rtol
@@ -205,9 +213,9 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
                                                   cov.C.M_dev.data_ptr())
         if name == "colorization":
             assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
-        if name == "custom_blur":
+        if name in _SHARED_PSF:
             assert torch.equal(op.taps.kernel, op0.taps.kernel), "lock-step images must share the PSF"
-        if name in _MASKED:
+        if name in _MASKED or name == "masked_blur":
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
             per.mask[b] = mk.data_ptr()
@@ -235,6 +243,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     else:
         ax = conv(x64, False)
         b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
+        if name == "masked_blur":  # b = M (y - B x0), each image with its own mask
+            b_vec = (torch.cat([k.view(1, 3, S, S) for k in keep[-B:]], 0) * b_vec).contiguous()
     sol = torch.empty_like(b_vec)
     rtol = rtol_func(sigma_t, max_rtol)
     rtols = (C.c_double * B)(*([rtol] * B))

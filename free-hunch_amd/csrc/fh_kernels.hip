@@ -1559,11 +1559,21 @@ __global__ __launch_bounds__(256) void k_conv_tile(const double* __restrict__ in
 // the LDS instruction rate (10 % of the f64 FMA rate on the 217-tap motion PSF); here a tap costs one 16-byte broadcast
 // read (weight + offset packed) and four two-address reads for 8 multiply-adds, and the halo is amortised over 4x the
 // outputs (2.9x the tile instead of 6.9x at the motion PSF's 58 x 16 extent).  Same tap order per output: same result.
-__global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ in, double* __restrict__ out,
-                                                    const int* __restrict__ tdy, const int* __restrict__ tdx,
-                                                    const double* __restrict__ tw, int ntaps, int S, int halo,
-                                                    int halo_x, int adjoint, const double* __restrict__ add,
-                                                    double add_scale, const fh_cg_state* __restrict__ states) {
+// MASKED (here and in k_conv1d / k_conv_window): the epilogue multiplies the convolution's result by the 0/1 mask of its
+// pixel before the `add` term, out = fma(add_scale, add, mask * t) - the expression of k_mask, so an all-ones mask gives the
+// bits of the unmasked kernel.  The mask of plane p is mk.D[p / 3] + (p % 3) S S (fh_batch.mask).  MASKED = false never touches
+// `mk`: the unmasked kernels are the code they were before the variant existed.
+template <bool MASKED>
+__device__ __forceinline__ const double* mask_plane(const fh_diag_tab& mk, int plane, int S) {
+  return MASKED ? mk.D[plane / 3] + (int64_t)(plane % 3) * S * S : nullptr;
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void conv_tile8_body(const double* __restrict__ in, double* __restrict__ out,
+                                                const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                const double* __restrict__ tw, int ntaps, int S, int halo, int halo_x,
+                                                int adjoint, const double* __restrict__ add, double add_scale,
+                                                const fh_cg_state* __restrict__ states, const fh_diag_tab& mk) {
   IMG_GUARD(states, blockIdx.z / 3);
   extern __shared__ __align__(16) double tile[];
   const conv_tile8_lds L(halo, halo_x, ntaps);
@@ -1588,6 +1598,7 @@ __global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ i
   __syncthreads();
   // thread = columns tx and tx + 16, rows ty + 16 r: 16 lanes read 16 consecutive doubles (all 32 banks of a half), the next
   // 16 lanes the next tile row - adjacent column PAIRS per lane would leave half of the banks idle in every pass
+  const double* mplane = mask_plane<MASKED>(mk, plane, S);
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
   const double* q = tile + (ty + halo) * sw + tx + halo_x;
   const int rstep = 16 * sw;
@@ -1613,11 +1624,29 @@ __global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ i
       if (oy < S && ox < S) {
         const int64_t o = (int64_t)plane * S * S + (int64_t)oy * S + ox;
         double v = a[r][e];
+        if (MASKED) v = mplane[(int64_t)oy * S + ox] * v;
         if (add != nullptr) v = fma(add_scale, add[o], v);
         out[o] = v;
       }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_conv_tile8(const double* __restrict__ in, double* __restrict__ out,
+                                                    const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                    const double* __restrict__ tw, int ntaps, int S, int halo,
+                                                    int halo_x, int adjoint, const double* __restrict__ add,
+                                                    double add_scale, const fh_cg_state* __restrict__ states) {
+  conv_tile8_body<false>(in, out, tdy, tdx, tw, ntaps, S, halo, halo_x, adjoint, add, add_scale, states, fh_diag_tab{});
+}
+
+__global__ __launch_bounds__(256) void k_conv_tile8_masked(const double* __restrict__ in, double* __restrict__ out,
+                                                           const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                           const double* __restrict__ tw, int ntaps, int S, int halo,
+                                                           int halo_x, int adjoint, const double* __restrict__ add,
+                                                           double add_scale, const fh_cg_state* __restrict__ states,
+                                                           fh_diag_tab mk) {
+  conv_tile8_body<true>(in, out, tdy, tdx, tw, ntaps, S, halo, halo_x, adjoint, add, add_scale, states, mk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1658,10 +1687,11 @@ __device__ __forceinline__ void window_block(const double* e, const double* ca, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_conv_window(const double* __restrict__ in, double* __restrict__ out,
-                                                     const double* __restrict__ win, int S, int hy, int hx, int adjoint,
-                                                     const double* __restrict__ add, double add_scale,
-                                                     const fh_cg_state* __restrict__ states) {
+template <bool MASKED>
+__device__ __forceinline__ void conv_window_body(const double* __restrict__ in, double* __restrict__ out,
+                                                 const double* __restrict__ win, int S, int hy, int hx, int adjoint,
+                                                 const double* __restrict__ add, double add_scale,
+                                                 const fh_cg_state* __restrict__ states, const fh_diag_tab& mk) {
   IMG_GUARD(states, blockIdx.z / 3);
   extern __shared__ __align__(16) double lds_win[];
   const conv_window_lds L(hy, hx);
@@ -1702,6 +1732,7 @@ __global__ __launch_bounds__(256) void k_conv_window(const double* __restrict__ 
   }
   const int oy = adjoint ? oy0 + py : oy0 + kWinH - 1 - py;
   if (oy >= S) return;
+  const double* mplane = mask_plane<MASKED>(mk, plane, S);
 #pragma unroll
   for (int r = 0; r < kWinR; ++r) {
     const int px = g * kWinR + r;
@@ -1709,10 +1740,25 @@ __global__ __launch_bounds__(256) void k_conv_window(const double* __restrict__ 
     if (ox < S) {
       const int64_t o = (int64_t)plane * S * S + (int64_t)oy * S + ox;
       double v = acc[r];
+      if (MASKED) v = mplane[(int64_t)oy * S + ox] * v;
       if (add != nullptr) v = fma(add_scale, add[o], v);
       out[o] = v;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_conv_window(const double* __restrict__ in, double* __restrict__ out,
+                                                     const double* __restrict__ win, int S, int hy, int hx, int adjoint,
+                                                     const double* __restrict__ add, double add_scale,
+                                                     const fh_cg_state* __restrict__ states) {
+  conv_window_body<false>(in, out, win, S, hy, hx, adjoint, add, add_scale, states, fh_diag_tab{});
+}
+
+__global__ __launch_bounds__(256) void k_conv_window_masked(const double* __restrict__ in, double* __restrict__ out,
+                                                            const double* __restrict__ win, int S, int hy, int hx,
+                                                            int adjoint, const double* __restrict__ add, double add_scale,
+                                                            const fh_cg_state* __restrict__ states, fh_diag_tab mk) {
+  conv_window_body<true>(in, out, win, S, hy, hx, adjoint, add, add_scale, states, mk);
 }
 
 __global__ __launch_bounds__(256) void k_conv_direct(const double* __restrict__ in, double* __restrict__ out,
@@ -2064,11 +2110,11 @@ __global__ __launch_bounds__(256) void k_woodbury_inner(PtrTab Msrct, int lds_, 
 // The tap list (ascending offsets, possibly with gaps) is expanded to a dense, zero-padded coefficient array in LDS:
 // e[k + h] multiplies in[p + k]; forward uses k = -offset, adjoint k = +offset (as k_conv_tile).
 // ------------------------------------------------------------------------------------------------
-template <int AXIS>
-__global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, double* __restrict__ out,
-                                                const int* __restrict__ toff, const double* __restrict__ tw,
-                                                int ntaps, int S, int h, int adjoint, const double* __restrict__ add,
-                                                double add_scale, const fh_cg_state* __restrict__ states) {
+template <int AXIS, bool MASKED>
+__device__ __forceinline__ void conv1d_body(const double* __restrict__ in, double* __restrict__ out,
+                                            const int* __restrict__ toff, const double* __restrict__ tw, int ntaps, int S,
+                                            int h, int adjoint, const double* __restrict__ add, double add_scale,
+                                            const fh_cg_state* __restrict__ states, const fh_diag_tab& mk) {
   IMG_GUARD(states, blockIdx.z / 3);
   extern __shared__ __align__(16) double lds1d[];
   const conv1d_lds L(h);
@@ -2134,6 +2180,7 @@ __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, d
     }
   }
   __syncthreads();  // tile is dead: reuse it to turn the results so that stores are coalesced along x
+  const double* mplane = mask_plane<MASKED>(mk, plane, S);
   if (AXIS == 0) {
     const int gx = c0 + lc;
 #pragma unroll
@@ -2142,6 +2189,7 @@ __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, d
       if (gx < S && gy < S) {
         const int64_t o = (int64_t)plane * S * S + (int64_t)gy * S + gx;
         double v = acc[r];
+        if (MASKED) v = mplane[(int64_t)gy * S + gx] * v;
         if (add != nullptr) v = fma(add_scale, add[o], v);
         out[o] = v;
       }
@@ -2157,11 +2205,29 @@ __global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, d
       if (gx < S && gy < S) {
         const int64_t o = (int64_t)plane * S * S + (int64_t)gy * S + gx;
         double v = turn[yy * (k1dAlong + 1) + xx];
+        if (MASKED) v = mplane[(int64_t)gy * S + gx] * v;
         if (add != nullptr) v = fma(add_scale, add[o], v);
         out[o] = v;
       }
     }
   }
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(256) void k_conv1d(const double* __restrict__ in, double* __restrict__ out,
+                                                const int* __restrict__ toff, const double* __restrict__ tw,
+                                                int ntaps, int S, int h, int adjoint, const double* __restrict__ add,
+                                                double add_scale, const fh_cg_state* __restrict__ states) {
+  conv1d_body<AXIS, false>(in, out, toff, tw, ntaps, S, h, adjoint, add, add_scale, states, fh_diag_tab{});
+}
+
+template <int AXIS>
+__global__ __launch_bounds__(256) void k_conv1d_masked(const double* __restrict__ in, double* __restrict__ out,
+                                                       const int* __restrict__ toff, const double* __restrict__ tw,
+                                                       int ntaps, int S, int h, int adjoint, const double* __restrict__ add,
+                                                       double add_scale, const fh_cg_state* __restrict__ states,
+                                                       fh_diag_tab mk) {
+  conv1d_body<AXIS, true>(in, out, toff, tw, ntaps, S, h, adjoint, add, add_scale, states, mk);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2244,12 +2310,35 @@ static int conv_plan_halo(int S, int ntaps, int halo, int planes, int stride, in
 
 static int conv_launch(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
                        const double* w, int ntaps, int halo, int planes, int stride, int adjoint, const double* add,
-                       double add_scale, const fh_cg_state* done, hipStream_t st) {
+                       double add_scale, const fh_cg_state* done, hipStream_t st, const fh_batch* masks = nullptr,
+                       double* spare = nullptr) {
+  // masks (ops 5 / 6, the pass that finishes B w): out = add_scale * add + mask .* conv(in).  k_conv1d and k_conv_tile8 do
+  // it in their epilogue; the other kernels write conv(in) to `spare` (a work vector of the caller's, not in / out / add)
+  // and k_mask finishes: one more streaming pass, the same bits
   const int S = ctx->S;
   conv_choice c;
   const int rc = conv_plan_halo(S, ntaps, halo, planes, stride, adjoint, &c);
   if (rc) return rc;
   const dim3 b(256);
+  if (masks != nullptr) {
+    if (stride != 1 || spare == nullptr || planes != 3 * masks->nimg) return FH_EINVAL;
+    fh_diag_tab mk;
+    memset(&mk, 0, sizeof(mk));
+    for (int i = 0; i < masks->nimg && i < FH_MAX_BATCH; ++i) mk.D[i] = masks->mask[i];
+    switch (c.kernel) {
+      case kConv1dCol: hipLaunchKernelGGL(k_conv1d_masked<0>, c.grid, b, c.lds, st, in, out, dy, w, ntaps, S, c.h, adjoint, add, add_scale, done, mk); break;
+      case kConv1dRow: hipLaunchKernelGGL(k_conv1d_masked<1>, c.grid, b, c.lds, st, in, out, dx, w, ntaps, S, c.h, adjoint, add, add_scale, done, mk); break;
+      case kConvTile8: hipLaunchKernelGGL(k_conv_tile8_masked, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, c.hy, c.hx, adjoint, add, add_scale, done, mk); break;
+      default: {
+        const int rc2 = conv_launch(ctx, in, spare, dy, dx, w, ntaps, halo, planes, stride, adjoint, nullptr, 0.0, done, st);
+        if (rc2) return rc2;
+        hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)masks->nimg), b, 0, st, *masks, (const double*)spare, add, add_scale,
+                           out, (int64_t)3 * S * S, done);
+      }
+    }
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
   switch (c.kernel) {
     case kConv1dCol: hipLaunchKernelGGL(k_conv1d<0>, c.grid, b, c.lds, st, in, out, dy, w, ntaps, S, c.h, adjoint, add, add_scale, done); break;
     case kConv1dRow: hipLaunchKernelGGL(k_conv1d<1>, c.grid, b, c.lds, st, in, out, dx, w, ntaps, S, c.h, adjoint, add, add_scale, done); break;
@@ -2273,17 +2362,28 @@ static int window_plan(int S, int hy, int hx, int planes, dim3* grid, size_t* ld
 }
 
 static int window_launch(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes,
-                         int adjoint, const double* add, double add_scale, const fh_cg_state* done, hipStream_t st) {
+                         int adjoint, const double* add, double add_scale, const fh_cg_state* done, hipStream_t st,
+                         const fh_batch* masks = nullptr) {
   dim3 grid;
   size_t lds;
   const int rc = window_plan(ctx->S, hy, hx, planes, &grid, &lds);
   if (rc) return rc;
+  if (masks != nullptr) {  // op 6: out = add_scale * add + mask .* conv(in) in the epilogue
+    if (planes != 3 * masks->nimg) return FH_EINVAL;
+    fh_diag_tab mk;
+    memset(&mk, 0, sizeof(mk));
+    for (int i = 0; i < masks->nimg && i < FH_MAX_BATCH; ++i) mk.D[i] = masks->mask[i];
+    hipLaunchKernelGGL(k_conv_window_masked, grid, dim3(256), lds, st, in, out, win, ctx->S, hy, hx, adjoint, add, add_scale,
+                       done, mk);
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
   hipLaunchKernelGGL(k_conv_window, grid, dim3(256), lds, st, in, out, win, ctx->S, hy, hx, adjoint, add, add_scale, done);
   FH_LAUNCH_CHECK();
   return 0;
 }
 
-// fh_problem.op = 4 (dense-window blur): tap_w is the window, halo = 64 hy + hx, and nothing of the tap-list operators is set
+// fh_problem.op = 4 / 6 (dense-window blur): tap_w is the window, halo = 64 hy + hx, and nothing of the tap-list operators is set
 static int window_problem_check(const fh_problem* p) {
   const int hy = p->halo / 64, hx = p->halo % 64;
   if (p->halo < 0 || hy > 32 || hx > 32 || p->ntaps != (2 * hy + 1) * (2 * hx + 1) || p->stride != 1) return FH_EINVAL;
@@ -2293,9 +2393,21 @@ static int window_problem_check(const fh_problem* p) {
 }
 
 // what fh_amm / fh_cg_solve[_batched] refuse before anything is launched
+// (the masks of a batched solve are per->mask[i]: masks_check)
 static int problem_check(const fh_problem* p) {
-  if (p->op < 0 || p->op > 4) return FH_EINVAL;
-  return p->op == 4 ? window_problem_check(p) : 0;
+  if (p->op < 0 || p->op > 6) return FH_EINVAL;
+  if (p->op >= 5 && p->stride != 1) return FH_EINVAL;
+  return p->op == 4 || p->op == 6 ? window_problem_check(p) : 0;
+}
+
+// ops 5 / 6 (masked blur): every image of the batch brings a mask
+static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
+static int masks_check(const fh_problem* p, const fh_batch& per) {
+  if (!masked_op(p)) return 0;
+  if (per.nimg < 1 || per.nimg > FH_MAX_BATCH) return FH_EINVAL;
+  for (int i = 0; i < per.nimg; ++i)
+    if (per.mask[i] == nullptr) return FH_EINVAL;
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2328,8 +2440,20 @@ static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch
   return 0;
 }
 
+// Masked blur (op = 5: the fields of op 1, op = 6: those of op 4, both with per.mask): A = M B, so
+//   A_mm(u) = sigma_y^2 u + M B C B^T M u.
+// The output-side M is applied by whichever pass finishes B w, as out = fma(sigma_y^2, u, mask * t): the table of the inverse
+// k_dct_sym pass, the masked epilogues of k_conv1d / k_conv_tile8 / k_conv_window, or a k_mask pass behind the kernels that
+// have no such epilogue (k_conv_tile, k_conv_direct, the dense folded passes on k_gemm_f64).
+// The input-side M is NOT applied here: the blur passes read `uin` (default u), and fh_amm hands in uin = M u.  The CG
+// leaves uin null, and that is exact, not approximate: fh_cg_solve_batched starts from x0 = M b, so r0 = M b - A_mm(M b) is
+// supported on the mask (off the mask A_mm(v) = sigma_y^2 v + 0 * t = 0 where v = 0), p0 = r0, and every later
+// r = r - alpha A p, p = r + beta p keeps that support; M p is then the product of every entry with exactly 1 or of a zero
+// with 0 - p itself, bit for bit.  So every iterate equals the one the fully masked operator would give.
 static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* u, double* out,
-                      const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr) {
+                      const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr,
+                      const double* uin = nullptr) {
+  if (uin == nullptr) uin = u;
   if (dot_nparts != nullptr) *dot_nparts = 0;
   static const bool no_dot_fuse = getenv("FH_CG_NO_DOT_FUSE") != nullptr;  // A/B switch
   if (no_dot_fuse) dot_part = nullptr;
@@ -2340,6 +2464,15 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   if (d != (int64_t)p->planes * S * S || p->planes != 3 || nimg < 1 || nimg > ctx->nimg_max) return FH_EINVAL;
   int rc = problem_check(p);
   if (rc) return rc;
+  rc = masks_check(p, per);
+  if (rc) return rc;
+  const bool blur = p->op == 1 || p->op == 5, window = p->op == 4 || p->op == 6;
+  const fh_batch* masks = masked_op(p) ? &per : nullptr;
+  fh_batch mdiag;  // the masks as the per-image table of k_dct_sym's epilogue (indexed by the natural output pixel)
+  memset(&mdiag, 0, sizeof(mdiag));
+  mdiag.nimg = nimg;
+  for (int i = 0; masks != nullptr && i < nimg; ++i) mdiag.D[i] = per.mask[i];
+  const fh_batch* mtab = masks != nullptr ? &mdiag : nullptr;
   double *w0 = ctx->w0, *w1 = ctx->w1;
   if (p->op == 3) {
     // colorization: u, out are ONE plane per image, A = channel mix with the three weights in tap_w.  The 2-D DCT acts per
@@ -2385,7 +2518,7 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   const dim3 egrid(512, 1, (unsigned)nimg);
   const bool sep = p->ntaps2 > 0;  // separable PSF: two 1-D passes (blur only, stride 1)
   if (sep && p->stride != 1) return FH_EINVAL;
-  if (p->op == 1 && p->use_dct && p->fold_fwd_w != nullptr) {
+  if (blur && p->use_dct && p->fold_fwd_w != nullptr) {
     // separable blur folded into the DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in 4 dense passes + the
     // apply, instead of 4 blur passes + 4 DCT passes + the apply + an axpy epilogue
     if (!p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
@@ -2393,38 +2526,46 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
       if (p->m == 0) {
         // no factor columns yet (every call above sigma = 10, i.e. three quarters of all CG iterations of a Heun-30 run): C z =
         // D .* z rides in the epilogue of the forward pass - two kernels per apply instead of three
-        rc = dct2d_launch_sym(ctx, u, w0, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st, &per);
+        rc = dct2d_launch_sym(ctx, uin, w0, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st, &per);
         if (rc) return rc;
-        return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, nullptr,
+        return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, mtab,
                                 dot_part, kCgScratch, dot_nparts);
       }
-      rc = dct2d_launch_sym(ctx, u, w1, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st);
+      rc = dct2d_launch_sym(ctx, uin, w1, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st);
       if (rc) return rc;
       rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
       if (rc) return rc;
-      return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, nullptr,
+      return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, mtab,
                               dot_part, kCgScratch, dot_nparts);
     }
-    rc = dct2d_launch_bases(ctx, u, w1, planes, p->fold_fwd_w, p->fold_fwd_h, nullptr, 0.0, states, st);
+    rc = dct2d_launch_bases(ctx, uin, w1, planes, p->fold_fwd_w, p->fold_fwd_h, nullptr, 0.0, states, st);
     if (rc) return rc;
     rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
     if (rc) return rc;
+    if (masks != nullptr) {  // k_gemm_f64 has no masked epilogue: B w to w1, then out = sigma_y^2 u + mask .* w1
+      rc = dct2d_launch_bases(ctx, w0, w1, planes, p->fold_inv_w, p->fold_inv_h, nullptr, 0.0, states, st);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out,
+                         d, states);
+      FH_LAUNCH_CHECK();
+      return 0;
+    }
     return dct2d_launch_bases(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, u, p->sigma_y2, states, st);
   }
   // w0 = A^T u
   if (p->op == 0) {
     hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, u, (const double*)nullptr, 0.0, w0, d, states);
-  } else if (p->op == 4) {
-    rc = window_launch(ctx, u, w0, p->tap_w, halo / 64, halo % 64, planes, 1, nullptr, 0.0, states, st);
+  } else if (window) {
+    rc = window_launch(ctx, uin, w0, p->tap_w, halo / 64, halo % 64, planes, 1, nullptr, 0.0, states, st);
     if (rc) return rc;
   } else if (sep) {
-    rc = conv_launch(ctx, u, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
+    rc = conv_launch(ctx, uin, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
                      states, st);
     if (rc) return rc;
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 1, nullptr, 0.0, states, st);
     if (rc) return rc;
   } else {
-    rc = conv_launch(ctx, u, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, 1, nullptr, 0.0,
+    rc = conv_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, 1, nullptr, 0.0,
                      states, st);
     if (rc) return rc;
   }
@@ -2450,18 +2591,18 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   // out = sigma_y^2 u + A w1
   if (p->op == 0) {
     hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out, d, states);
-  } else if (p->op == 4) {
-    rc = window_launch(ctx, w1, out, p->tap_w, halo / 64, halo % 64, planes, 0, u, p->sigma_y2, states, st);
+  } else if (window) {
+    rc = window_launch(ctx, w1, out, p->tap_w, halo / 64, halo % 64, planes, 0, u, p->sigma_y2, states, st, masks);
     if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
     if (rc) return rc;
     rc = conv_launch(ctx, w0, out, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 0, u, p->sigma_y2,
-                     states, st);
+                     states, st, masks, w1);  // (w1 has been read: it is the spare of a pass without a masked epilogue)
     if (rc) return rc;
   } else {
     rc = conv_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, 0, u, p->sigma_y2,
-                     states, st);
+                     states, st, masks, w0);
     if (rc) return rc;
   }
   FH_LAUNCH_CHECK();
@@ -2636,7 +2777,8 @@ static int set_kernel_attributes() {
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
   for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
-  FH_CHECK(hipFuncSetAttribute((const void*)k_conv_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
+  for (const void* fn : {(const void*)k_conv_window, (const void*)k_conv_window_masked})
+    FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
   return 0;
 }
 
@@ -3224,8 +3366,16 @@ int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, v
   if (problem_check(p)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)u | (uintptr_t)out) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const fh_batch per = batch_of(p);
+  if (masks_check(p, per)) return FH_EINVAL;
   const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
   if (rc) return rc;
+  if (masked_op(p)) {  // the input-side mask of A_mm (amm_launch): M u into a CG vector, which is idle outside a solve
+    if (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3) return FH_EINVAL;
+    if (ctx->planes_max < 3) return FH_ESIZE;
+    hipLaunchKernelGGL(k_mask, dim3(512, 1, 1), dim3(256), 0, (hipStream_t)stream, per, u, (const double*)nullptr, 0.0, ctx->cg_p,
+                       p->d, (const fh_cg_state*)nullptr);
+    return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, ctx->cg_p);
+  }
   return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
 }
 
@@ -3319,7 +3469,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (nimg < 1 || nimg > ctx->nimg_max || nimg > FH_MAX_BATCH) return FH_ESIZE;
   hipStream_t st = (hipStream_t)stream;
   const int S = ctx->S;
-  if (problem_check(p) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
+  if (problem_check(p) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const int So = S / (p->op == 2 ? p->stride : 1);
   const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)
@@ -3333,7 +3483,21 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
     if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
   int rc = colorize_prepare(ctx, p, per, st);
   if (rc) return rc;
-  if (!p->cg_scipy) {
+  if (masked_op(p)) {
+    // masked blur: the system is solved for M b - the one masking of a solve; the iteration then needs no input-side mask
+    // (amm_launch).  M b goes to cg_x for the first apply and, once that has released the work vectors, to w0 for k_cg_init
+    if (p->d != n || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
+    const dim3 mgrid(512, 1, (unsigned)nimg);
+    hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->cg_x, n,
+                       (const fh_cg_state*)nullptr);
+    if (!p->cg_scipy) {
+      rc = amm_launch(ctx, p, per, ctx->cg_x, ap, nullptr, st);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->w0, n,
+                       (const fh_cg_state*)nullptr);
+    b = ctx->w0;
+  } else if (!p->cg_scipy) {
     rc = amm_launch(ctx, p, per, b, ap, nullptr, st);  // A x0 with x0 = b
     if (rc) return rc;
   }

@@ -288,6 +288,74 @@ class CustomBlurOperator(_BlurOperator):
         self.in_shape = in_shape
 
 
+@register_operator(name="masked_blur")
+class MaskedBlurOperator(CustomBlurOperator):
+    """Blur with a validity mask, y = M (B x + n): B the circular blur of `custom_blur` (same PSF arguments, same checks,
+    same kernels), M a 0/1 mask (1 = pixel measured) that drops what the circular model cannot explain - saturated, dead or
+    occluded pixels, and the band along the edges that a real camera did not wrap around.
+      mask        array / tensor [S,S], [3,S,S] or [1,3,S,S], entries exactly 0 or 1
+      mask_path   a .npy of the same shapes (instead of `mask`)
+      mask_border N >= 0: N pixels on every side are dropped; -1: the PSF's reach, hy rows top and bottom, hx columns left
+                  and right (`taps.hy`, `taps.hx`)
+    Border and array multiply.  `mask` is [1,3,S,S] on the device, like InpaintingOperator.mask."""
+
+    def __init__(self, in_shape, sigma_s, device, kernel_path=None, kernel=None, mask=None, mask_path=None, mask_border=0,
+                 **kwargs):
+        super().__init__(in_shape, sigma_s, device, kernel_path=kernel_path, kernel=kernel)
+        S = int(in_shape[-1])
+        mask_path = mask_path or None
+        mask_border = int(mask_border or 0)
+        if mask is not None and mask_path is not None:
+            raise ValueError("masked_blur takes mask (an array) or mask_path (a .npy file), not both")
+        if mask is None and mask_path is None and mask_border == 0:
+            raise ValueError("masked_blur needs a mask: mask, mask_path or a non-zero mask_border (for a blur without a mask "
+                             "use custom_blur)")
+        if mask_border < -1:
+            raise ValueError(f"masked_blur: mask_border is a pixel count >= 0, or -1 for the PSF's reach; got {mask_border}")
+        m = np.ones((1, 3, S, S))
+        if mask is not None or mask_path is not None:
+            a = np.load(mask_path) if mask is None else (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask))
+            if tuple(a.shape) not in ((S, S), (3, S, S), (1, 3, S, S)):
+                raise ValueError(f"masked_blur: the mask must have shape ({S}, {S}), (3, {S}, {S}) or (1, 3, {S}, {S}), got "
+                                 f"{tuple(a.shape)}")
+            a = np.asarray(a, dtype=np.float64)
+            if not np.isfinite(a).all():
+                raise ValueError("masked_blur: the mask has a non-finite entry")
+            if not np.isin(a, (0.0, 1.0)).all():
+                raise ValueError("masked_blur: the mask has an entry other than 0 and 1 (per-pixel weights are not supported)")
+            m = m * a.reshape((1, 1, S, S) if a.ndim == 2 else (1, 3, S, S))
+        by, bx = (self.taps.hy, self.taps.hx) if mask_border == -1 else (mask_border, mask_border)
+        if 2 * max(by, bx) >= S:
+            raise ValueError(f"masked_blur: a border of ({by}, {bx}) pixels on every side leaves nothing of a {S} x {S} image")
+        if by > 0:
+            m[..., :by, :] = 0.0
+            m[..., S - by:, :] = 0.0
+        if bx > 0:
+            m[..., :, :bx] = 0.0
+            m[..., :, S - bx:] = 0.0
+        if not m.any():
+            raise ValueError("masked_blur: the mask (array times border) is all zero - no pixel is measured")
+        self.mask_border = (by, bx)
+        self.mask = torch.from_numpy(m).to(self.device)  # float64 [1,3,S,S]
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # the noise is drawn for the full image (custom_blur's RNG consumption), then masked
+        y = self._noise(self._conv(data).to(data.dtype), noiseless) * self.mask.to(data.dtype)
+        self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.in_shape[-3:])
+        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`: B^T (mask * v)"""
+        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
+
+
 def _cubic(x):
     ax = np.abs(x)
     return ((1.5 * ax ** 3 - 2.5 * ax ** 2 + 1) * (ax <= 1)

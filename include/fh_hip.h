@@ -225,6 +225,15 @@ typedef struct fh_problem {
    * forward and one inverse DCT over one plane per image, and with m = 0 it is idct2(D_eff .* dct2(u)), D_eff = sum_c w_c^2 D_c.
    * 4 dense-window blur: A = fh_conv_window with the window in tap_w, halo = 64 * hy + hx, ntaps = (2 hy + 1)(2 hx + 1),
    * stride = 1; tap_dy, tap_dx, tap2_* and fold_* null and ntaps2 = 0 (anything else: FH_EINVAL before any launch).
+   * 5 masked blur: y = M (B x + n), A = M B with B the stride-1 blur of op = 1 and M = diag(mask), mask entries exactly 0 or 1
+   * (1 = pixel measured; the wrapped border band and bad pixels are 0).  Every field as for op = 1 - tap list, optional second
+   * separable pass, optional folded bases with or without fold_sym - plus mask != NULL ([d], the mask of plane p at
+   * mask + (p % 3) S S); stride = 1.  The measurement - u, b, x - stays full size, [3][S][S] per image, as for inpainting:
+   *   fh_amm:   A_mm(u) = sigma_y2 u + M B C B^T M u for an arbitrary u (the input is masked too), = sigma_y2 u exactly off the mask;
+   *   fh_cg_solve[_batched]: solves for M b (b is masked once, at the start) and returns x that is exactly zero off the mask.
+   * An all-ones mask gives the bits of op = 1.  6 masked dense-window blur: the same with B the window of op = 4 - every field as
+   * for op = 4 and every refusal of op = 4, plus mask != NULL; an all-ones mask gives the bits of op = 4.  A null mask or
+   * stride != 1: FH_EINVAL before any launch.
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
@@ -239,7 +248,7 @@ typedef struct fh_problem {
   const int32_t* tap_dy; /* [ntaps] */
   const int32_t* tap_dx;
   const double* tap_w;
-  const double* mask;    /* [d] 0/1 (inpainting) */
+  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement) */
   const double* D;       /* covariance rep: diag, row scale, base, inner matrix */
   const double* r;
   const double* B;
@@ -270,7 +279,8 @@ typedef struct fh_problem {
 } fh_problem;
 
 /* Per-image covariance pointers of a batched solve: B images share the operator, the tap lists, m, ldm and
- * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these. */
+ * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5 and 6 read
+ * mask[i], which may differ from image to image (ops 5 / 6: all non-null, else FH_EINVAL; the PSF is shared). */
 #define FH_MAX_BATCH 16
 typedef struct fh_batch {
   int32_t nimg;
