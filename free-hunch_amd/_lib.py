@@ -57,6 +57,8 @@ _SIGS = {
     "fh_debug_read_stamps": ([C.c_void_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_void_p], C.c_int),
     "fh_dct2d": ([C.c_void_p, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_dct_sym_plan": ([C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_int64)], C.c_int),
+    "fh_dct_rect": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
+    "fh_dct_rect_plan": ([C.c_int] * 4 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_dct_moments_u8": ([C.c_void_p, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_rep_apply": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
     "fh_rep_apply_batched": ([C.c_void_p, C.POINTER(FhBatch), C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
@@ -222,6 +224,17 @@ class Context:
         out = torch.empty_like(x) if out is None else out
         planes = x.numel() // (self.S * self.S)
         check(self.lib.fh_dct2d(self.h, ptr(x), ptr(out), planes, int(inverse), stream()), "fh_dct2d")
+        return out
+
+    def dct_rect(self, x, out, P_w, P_h, So, inverse=False):
+        """out = P_h x P_w^T per plane (fh_dct_rect): x [planes,So,So] -> out [planes,S,S] with [S][So] bases, or the inverse
+        shapes with [So][S] bases"""
+        a, b = (self.S, So) if inverse else (So, self.S)
+        planes = x.numel() // (a * a)
+        assert x.dtype == out.dtype == P_w.dtype == P_h.dtype == torch.float64
+        assert x.numel() == planes * a * a and out.numel() == planes * b * b and P_w.numel() == P_h.numel() == self.S * So
+        check(self.lib.fh_dct_rect(self.h, ptr(x), ptr(out), ptr(P_w), ptr(P_h), So, planes, int(inverse), stream()),
+              "fh_dct_rect")
         return out
 
     def dct_moments_u8(self, imgs, work, sum_, sumsq):

@@ -63,13 +63,15 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 
 
 # fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
-# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, see _problem)
+# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
+# into rectangular DCT bases op = 7, see _problem)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
-            "noise": 0, "masked_blur": 5}
+            "noise": 0, "masked_blur": 5, "custom_sr": 2}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
-_SHARED_PSF = ("custom_blur", "masked_blur")  # operators whose PSF is the caller's: a lock-step batch must share it
+_SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr")  # operators whose PSF is the caller's: a lock-step batch must share it
+_DECIMATING = ("super_resolution", "custom_sr")  # operators with a scale_factor: A = blur + decimation on the PSF's tap list
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', 'noise', 'custom_blur', or 'masked_blur'.")
+                 "'colorization', 'noise', 'custom_blur', 'masked_blur', or 'custom_sr'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -85,7 +87,7 @@ def _problem(operator, cov, sigma_y2):
     p.op = _OP_CODE[operator.name]
     p.use_dct = int(cov.use_dct)
     p.planes = 3
-    p.stride = int(operator.scale_factor) if operator.name == "super_resolution" else 1
+    p.stride = int(operator.scale_factor) if operator.name in _DECIMATING else 1
     p.d = cov.data_dim
     p.sigma_y2 = sigma_y2
     m = cov.famC.m
@@ -107,7 +109,7 @@ def _problem(operator, cov, sigma_y2):
         keep.append(win)
     else:
         t = operator.taps
-        if t.sep is not None and operator.name != "super_resolution":
+        if t.sep is not None and operator.name not in _DECIMATING:
             t, t2 = t.sep
             p.ntaps2, p.halo2 = t2.n, t2.halo
             p.tap2_dy, p.tap2_dx, p.tap2_w = t2.dy.data_ptr(), t2.dx.data_ptr(), t2.w.data_ptr()
@@ -119,6 +121,11 @@ def _problem(operator, cov, sigma_y2):
             p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in mats)
             p.fold_sym = int(sym)
             keep.extend(mats)
+        sr = operator.folded_sr_bases() if (cov.use_dct and operator.name == "custom_sr") else None
+        if sr is not None:  # rank-1 PSF + decimation absorbed by rectangular DCT bases (measurements.folded_dct_sr_bases)
+            p.op = 7
+            p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in sr)
+            keep.extend(sr)
     if operator.name == "masked_blur":  # A = M B: the mask rides with the blur's fields (ops 5 / 6); kept LAST in `keep`
         mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
         p.mask = mask.data_ptr()
@@ -130,7 +137,7 @@ def _sigma_y2(operator):
     """`sigma_s.clip(min=0.001)**2` evaluated in float32 like the reference (:386, :491), SR also clips at 1e-2 (:642);
     colorization and denoising follow the blur / inpainting rule."""
     s = operator.sigma_s.detach().cpu().float().clip(min=0.001)
-    if operator.name == "super_resolution":
+    if operator.name in _DECIMATING:
         s = s.clip(min=1e-2)
     return float((s ** 2).item())
 
@@ -215,6 +222,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
         if name in _SHARED_PSF:
             assert torch.equal(op.taps.kernel, op0.taps.kernel), "lock-step images must share the PSF"
+        if name in _DECIMATING:
+            assert op.scale_factor == op0.scale_factor, "lock-step images must share the scale_factor"
         if name in _MASKED or name == "masked_blur":
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)

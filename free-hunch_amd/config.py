@@ -46,7 +46,8 @@ SCHEMA = {
     # NEW: the two weight files of LPIPS-VGG (torchvision's vgg16-397923af.pth, lpips' weights/v0.1/vgg.pth); both empty =
     # no LPIPS line in results.txt
     "lpips_vgg_path": (str, ""), "lpips_lin_path": (str, ""),
-    # NEW: the PSF of --operator_name=custom_blur, a 2-D .npy (used as given, not normalised; up to 65 x 65)
+    # NEW: the PSF of --operator_name=custom_blur, a 2-D .npy (used as given, not normalised; up to 65 x 65); also the PSF of
+    # --operator_name=masked_blur and of --operator_name=custom_sr (blur, then every --scale_factor-th sample: 2 .. 16)
     "kernel_path": (str, ""),
     # NEW: the validity mask of --operator_name=masked_blur (y = M (B x + n), the PSF from --kernel_path): a 0/1 .npy of shape
     # [S,S], [3,S,S] or [1,3,S,S], and / or a border of N dropped pixels on every side (-1: the PSF's reach); the two multiply
@@ -84,10 +85,12 @@ def load_config(argv=None):
         if not cfg["mask_path"] and cfg["mask_border"] == 0:
             raise SystemExit("--operator_name=masked_blur needs a mask: --mask_path=FILE.npy and / or --mask_border=N (without a "
                              "mask use --operator_name=custom_blur)")
-    elif cfg["mask_path"] or cfg["mask_border"] != 0:
+    if cfg["operator_name"] == "custom_sr" and not cfg["kernel_path"]:
+        raise SystemExit("--operator_name=custom_sr needs --kernel_path=FILE.npy (the PSF, a 2-D array) beside --scale_factor")
+    if cfg["operator_name"] != "masked_blur" and (cfg["mask_path"] or cfg["mask_border"] != 0):
         raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
-    if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur"):
-        raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur; operator "
+    if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr"):
+        raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr; operator "
                          f"'{cfg['operator_name']}' does not read it")
     return SimpleNamespace(**cfg)

@@ -365,6 +365,132 @@ __global__ __launch_bounds__(256 * NS) void k_dct_sym(const double* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rectangular form of the transposed-result pass (k_dct_rect): per plane  out[k][r] = sum_n P[k][n] in[r][n]  with
+// P [KO][KI], in [R][KI], out [KO][R].  Blur + decimation by s of a rank-1 PSF fold into the DCT bases as the stride-1 blur
+// does (fh_problem.op = 7): G[k][j] = P[k][j s] is [S][So], So = S / s, and
+//     dct2(A^T u) = G_col u G_row^T :  pass A  P = G_row,   in u [So][So] -> [S][So];   pass B  P = G_col,   -> [S][S]
+//     A(idct2(v)) = G_col^T v G_row :  pass A  P = G_row^T, in v [S][S]   -> [So][S];   pass B  P = G_col^T, -> [So][So]
+// The subsampled bases have no mirror symmetry, so these are dense products - but of S S So (S + So) multiply-adds per
+// plane pair instead of S^3.  A workgroup owns 32 (k) x 32 (r) outputs, keeps its 32-row slice of P (zero padded to whole
+// K chunks of 32, at most 32 x 258 doubles) RESIDENT in LDS and walks over its share of the planes (z, z + gridDim.z, ...),
+// the next chunk of `in` prefetched into registers while the current one is multiplied.  Same MFMA
+// (v_mfma_f64_16x16x4_f64), operand maps and row pitch rule (pitch = 2 mod 32 doubles) as k_gemm_f64 / k_dct_sym.  Ragged
+// KO, KI and R are zero padded under guards; zero terms leave an accumulator as it is, so every output is ONE chain of
+// accumulations with k ascending in steps of 4 and does not depend on the planes, the batch or the launch.
+// Epilogue operands as in k_dct_sym: the per-image done flag, the per-image table dg (forward pass B: C z = D .* z for
+// m = 0), add / add_scale and the p.Ap block partials dot_part (inverse pass B).
+// ------------------------------------------------------------------------------------------------
+template <int PPI = 3>
+__global__ __launch_bounds__(256) void k_dct_rect(const double* __restrict__ P, const double* __restrict__ X,
+                                                  double* __restrict__ C, int KO, int KI, int R, int planes,
+                                                  const fh_cg_state* __restrict__ states, const double* __restrict__ add,
+                                                  double add_scale, fh_diag_tab dg, double* __restrict__ dot_part,
+                                                  int dot_stride) {
+  constexpr int TJ = 32, TR = 32, BK = 32, LDB = BK + 2;
+  extern __shared__ __align__(16) double smem[];
+  const int nkc = (KI + BK - 1) / BK, KP = nkc * BK, LDA = KP + 2;
+  double* As = smem;             // [TJ][LDA] resident slice of P, zero beyond KO / KI
+  double* Bs = As + TJ * LDA;    // [2 buffers][TR][LDB]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lk = lane >> 4;
+  const int jw = (wave >> 1) * 16, rw = (wave & 1) * 16;
+  const int j0 = blockIdx.y * TJ, r0 = blockIdx.x * TR;
+  const int gz = (int)gridDim.z;
+  // the next plane of this workgroup's list at or after p whose image is still running (uniform: scalar loads)
+  auto live = [&](int p) {
+    while (p < planes && states != nullptr && states[p / PPI].done != 0) p += gz;
+    return p;
+  };
+  int p = live((int)blockIdx.z);
+  if (p >= planes) return;  // (uniform over the workgroup)
+  const bool pvec = (KI & 1) == 0 && ((uintptr_t)P & 15) == 0, xvec = (KI & 1) == 0 && ((uintptr_t)X & 15) == 0;
+  for (int i = tid; i < TJ * (KP / 2); i += 256) {
+    const int row = i / (KP / 2), c2 = (i % (KP / 2)) * 2;
+    const bool in_row = j0 + row < KO;
+    const double* src = P + (int64_t)(j0 + row) * KI + c2;
+    double2 v = make_double2(0.0, 0.0);
+    if (in_row && pvec && c2 + 2 <= KI) {
+      v = *reinterpret_cast<const double2*>(src);
+    } else if (in_row) {
+      if (c2 < KI) v.x = src[0];
+      if (c2 + 1 < KI) v.y = src[1];
+    }
+    *reinterpret_cast<double2*>(&As[row * LDA + c2]) = v;
+  }
+  // staging: 32 rows x 32 k per chunk = 4 doubles per thread: row tid >> 3 of the r tile, k segment (tid & 7) * 4
+  const int srow = tid >> 3, sseg = (tid & 7) * 4;
+  double ra[4];
+  auto load_chunk = [&](int pp, int kc) {
+    const int gr = r0 + srow, gk = kc * BK + sseg;
+    const double* row = X + (int64_t)pp * R * KI + (int64_t)gr * KI + gk;
+    if (gr < R && xvec && gk + 4 <= KI) {
+      const double2 a0 = reinterpret_cast<const double2*>(row)[0], a1 = reinterpret_cast<const double2*>(row)[1];
+      ra[0] = a0.x, ra[1] = a0.y, ra[2] = a1.x, ra[3] = a1.y;
+      return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ra[e] = (gr < R && gk + e < KI) ? row[e] : 0.0;
+  };
+  auto store_chunk = [&](int buf) {
+    double* dst = Bs + (buf * TR + srow) * LDB + sseg;
+    *reinterpret_cast<double2*>(dst) = make_double2(ra[0], ra[1]);
+    *reinterpret_cast<double2*>(dst + 2) = make_double2(ra[2], ra[3]);
+  };
+  load_chunk(p, 0);
+  store_chunk(0);
+  __syncthreads();
+  double4_t acc = {0.0, 0.0, 0.0, 0.0};
+  const int tiles = (int)(gridDim.x * gridDim.y), tile = (int)(blockIdx.y * gridDim.x + blockIdx.x);
+  int buf = 0, kc = 0;
+  while (true) {
+    int np = p, nk = kc + 1;
+    if (nk == nkc) nk = 0, np = live(p + gz);
+    const bool more = np < planes;
+    if (more) load_chunk(np, nk);
+    const double* a = As + (jw + li) * LDA + kc * BK + lk;
+    const double* b = Bs + (buf * TR + rw + li) * LDB + lk;
+#pragma unroll
+    for (int kk = 0; kk < BK; kk += 4) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kk], b[kk], acc, 0, 0, 0);
+    if (kc == nkc - 1) {  // plane p is complete (kc and p are uniform)
+      double* Cp = C + (int64_t)p * KO * R;
+      const double* Ap = add != nullptr ? add + (int64_t)p * KO * R : nullptr;
+      const double* Dp = dg.D[0] != nullptr ? dg.D[p / PPI] + (int64_t)(p % PPI) * KO * R : nullptr;
+      const int col = r0 + rw + li;
+      double dsum = 0.0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int jj = j0 + jw + lk + 4 * q;
+        if (jj < KO && col < R) {
+          const int64_t o = (int64_t)jj * R + col;
+          double v = acc[q];
+          if (Dp != nullptr) v = Dp[o] * v;  // same product as k_rep_apply2 forms for m = 0
+          if (Ap != nullptr) {
+            const double a0 = Ap[o];
+            v = fma(add_scale, a0, v);
+            dsum = fma(a0, v, dsum);
+          }
+          Cp[o] = v;
+        }
+      }
+      acc = double4_t{0.0, 0.0, 0.0, 0.0};
+      if (dot_part != nullptr) {  // (uniform) sum(add .* out) of this (plane, tile), as k_dct_sym leaves it
+        __shared__ double dred[4];
+        dsum = wave_sum(dsum);
+        __syncthreads();
+        if (lane == 0) dred[wave] = dsum;
+        __syncthreads();
+        if (tid == 0)
+          dot_part[(int64_t)(p / PPI) * dot_stride + (p % PPI) * tiles + tile] = dred[0] + dred[1] + dred[2] + dred[3];
+      }
+    }
+    if (more) store_chunk(buf ^ 1);
+    __syncthreads();
+    if (!more) break;
+    p = np, kc = nk, buf ^= 1;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // DCT-variance prior (fh_dct_moments_u8): ingest and moments around the DCT passes.  Both are streaming kernels over a
 // few MB; the tool they serve is bound by image decoding, so nothing here goes beyond coalesced 16-byte accesses.
 // ------------------------------------------------------------------------------------------------
@@ -521,6 +647,69 @@ static int dct2d_launch(fh_context* ctx, const double* in, double* out, int plan
   }
   const double* b1 = inverse ? ctx->basis_t : ctx->basis;
   return dct2d_launch_bases(ctx, in, out, planes, b1, b1, add, add_scale, states, st, ppi);
+}
+
+// Launch plan of one rectangular pass (host arithmetic only): 32 x 32 output tiles, and over z as few workgroups as walk the
+// planes in the same number of trips as one workgroup per CU would (24 planes on 16 tiles: 12 x 2 planes, not 16 x 1 or 2).
+struct dct_rect_plan_t {
+  int gx, gy, gz;
+  int64_t lds_bytes;
+};
+static dct_rect_plan_t dct_rect_plan(int KO, int KI, int R, int planes) {
+  dct_rect_plan_t pn;
+  pn.gx = (R + 31) / 32, pn.gy = (KO + 31) / 32;
+  int cap = 256 / (pn.gx * pn.gy);
+  if (cap < 1) cap = 1;
+  if (cap > planes) cap = planes;
+  const int trips = (planes + cap - 1) / cap;
+  pn.gz = (planes + trips - 1) / trips;
+  // doubles: the resident slice [32][KI padded to chunks of 32, + 2], then two [32][34] staging buffers
+  pn.lds_bytes = ((int64_t)32 * ((KI + 31) / 32 * 32 + 2) + (int64_t)2 * 32 * 34) * (int64_t)sizeof(double);
+  return pn;
+}
+constexpr int64_t kLdsRect = 140 * 1024;  // the opt-in of set_kernel_attributes (k_dct_sym's)
+
+// (KO, KI, R) of pass A and pass B of a rectangular pair at image side S and measurement side So
+static void dct_rect_shapes(int S, int So, int inverse, int shp[2][3]) {
+  const int a[3] = {inverse ? So : S, inverse ? S : So, inverse ? S : So};
+  const int b[3] = {inverse ? So : S, inverse ? S : So, inverse ? So : S};
+  memcpy(shp[0], a, sizeof(a));
+  memcpy(shp[1], b, sizeof(b));
+}
+
+static bool dct_rect_sizes_ok(int S, int So, int planes) {
+  return S >= 2 && S <= 256 && (S & 1) == 0 && So >= 1 && So <= S && planes >= 1 && planes <= 65535;
+}
+
+// the two rectangular passes: forward  out [S][S] = P_h u P_w^T of u [So][So] (P_w, P_h [S][So]), inverse
+// out [So][So] = P_h v P_w^T of v [S][S] (P_w, P_h [So][S]), (+ add_scale * add); tmp = the transposed result of pass A
+static int dct_rect_launch(fh_context* ctx, const double* in, double* out, int planes, const double* P_w, const double* P_h,
+                           int So, int inverse, const double* add, double add_scale, const fh_cg_state* states, hipStream_t st,
+                           const fh_batch* diag = nullptr, double* dot_part = nullptr, int dot_stride = 0,
+                           int* dot_nparts = nullptr) {
+  const int S = ctx->S;
+  if (dot_nparts != nullptr) *dot_nparts = 0;
+  if (!dct_rect_sizes_ok(S, So, planes)) return FH_EINVAL;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  int shp[2][3];
+  dct_rect_shapes(S, So, inverse, shp);
+  const dct_rect_plan_t pa = dct_rect_plan(shp[0][0], shp[0][1], shp[0][2], planes);
+  const dct_rect_plan_t pb = dct_rect_plan(shp[1][0], shp[1][1], shp[1][2], planes);
+  if (pa.lds_bytes > kLdsRect || pb.lds_bytes > kLdsRect) return FH_ESIZE;
+  fh_diag_tab none, dg;
+  memset(&none, 0, sizeof(none));
+  memset(&dg, 0, sizeof(dg));
+  if (diag != nullptr)
+    for (int i = 0; i < diag->nimg && i < FH_MAX_BATCH; ++i) dg.D[i] = diag->D[i];
+  if (add == nullptr || 3 * pb.gx * pb.gy > 256) dot_part = nullptr;  // (the consumer sums <= 256 partials per image)
+  if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? 3 * pb.gx * pb.gy : 0;
+  hipLaunchKernelGGL(k_dct_rect<3>, dim3(pa.gx, pa.gy, pa.gz), dim3(256), (size_t)pa.lds_bytes, st, P_w, in, ctx->tmp_img,
+                     shp[0][0], shp[0][1], shp[0][2], planes, states, (const double*)nullptr, 0.0, none, (double*)nullptr, 0);
+  hipLaunchKernelGGL(k_dct_rect<3>, dim3(pb.gx, pb.gy, pb.gz), dim3(256), (size_t)pb.lds_bytes, st, P_h,
+                     (const double*)ctx->tmp_img, out, shp[1][0], shp[1][1], shp[1][2], planes, states, add, add_scale, dg,
+                     dot_part, dot_stride);
+  FH_LAUNCH_CHECK();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2394,8 +2583,14 @@ static int window_problem_check(const fh_problem* p) {
 
 // what fh_amm / fh_cg_solve[_batched] refuse before anything is launched
 // (the masks of a batched solve are per->mask[i]: masks_check)
-static int problem_check(const fh_problem* p) {
-  if (p->op < 0 || p->op > 6) return FH_EINVAL;
+// S: the context's image side
+static int problem_check(const fh_problem* p, int S) {
+  if (p->op < 0 || p->op > 7) return FH_EINVAL;
+  if (p->op == 7) {  // separable SR on folded rectangular bases: the four [S][S / stride] / [S / stride][S] bases, no mask
+    if (p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0 || p->mask != nullptr) return FH_EINVAL;
+    if (!p->fold_fwd_w || !p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
+    return 0;
+  }
   if (p->op >= 5 && p->stride != 1) return FH_EINVAL;
   return p->op == 4 || p->op == 6 ? window_problem_check(p) : 0;
 }
@@ -2403,6 +2598,11 @@ static int problem_check(const fh_problem* p) {
 // ops 5 / 6 (masked blur): every image of the batch brings a mask
 static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
 static int masks_check(const fh_problem* p, const fh_batch& per) {
+  if (p->op == 7) {  // no mask on the low-resolution measurement
+    for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
+      if (per.mask[i] != nullptr) return FH_EINVAL;
+    return 0;
+  }
   if (!masked_op(p)) return 0;
   if (per.nimg < 1 || per.nimg > FH_MAX_BATCH) return FH_EINVAL;
   for (int i = 0; i < per.nimg; ++i)
@@ -2462,7 +2662,7 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   const int nimg = per.nimg;
   const int planes = p->planes * nimg;
   if (d != (int64_t)p->planes * S * S || p->planes != 3 || nimg < 1 || nimg > ctx->nimg_max) return FH_EINVAL;
-  int rc = problem_check(p);
+  int rc = problem_check(p, S);
   if (rc) return rc;
   rc = masks_check(p, per);
   if (rc) return rc;
@@ -2513,6 +2713,23 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     hipLaunchKernelGGL(k_channel_mix<false>, cgrid, dim3(256), 0, st, (const double*)w1, w0, cw, pairs, (const double*)nullptr,
                        0.0, states);
     return dct2d_launch(ctx, w0, out, nimg, 1, states, st, 1, u, p->sigma_y2, dot_part, kCgScratch, dot_nparts);
+  }
+  if (p->op == 7) {
+    // rank-1 PSF + decimation folded into rectangular DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in four small
+    // dense passes + the apply; u, out are [3][So][So] per image.  With no factor columns C z = D .* z rides in forward pass B.
+    const int So = S / p->stride;
+    if (planes > ctx->planes_max) return FH_ESIZE;
+    if (p->m == 0) {
+      rc = dct_rect_launch(ctx, u, w0, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st, &per);
+      if (rc) return rc;
+    } else {
+      rc = dct_rect_launch(ctx, u, w1, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st);
+      if (rc) return rc;
+      rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
+      if (rc) return rc;
+    }
+    return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, So, 1, u, p->sigma_y2, states, st, nullptr,
+                           dot_part, kCgScratch, dot_nparts);
   }
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
@@ -2773,7 +2990,7 @@ static int set_kernel_attributes() {
                                  (const void*)k_dct_sym<false, 1>,    (const void*)k_dct_sym<true, 1>,
                                  (const void*)k_dct_sym<false, 3, 2>, (const void*)k_dct_sym<true, 3, 2>,
                                  (const void*)k_dct_sym<false, 1, 2>, (const void*)k_dct_sym<true, 1, 2>,
-                                 (const void*)k_woodbury_inner};
+                                 (const void*)k_woodbury_inner,       (const void*)k_dct_rect<3>};
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
   for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
@@ -2933,6 +3150,29 @@ int fh_dct_sym_plan(int S, int planes, int* gx, int* gy, int* gz, int* ns, int64
   const dct_sym_plan_t pn = dct_sym_plan(S, planes);
   *gx = pn.gx, *gy = pn.gy, *gz = pn.gz, *ns = pn.ns, *lds_bytes = pn.lds_bytes;
   return 0;
+}
+
+int fh_dct_rect_plan(int S, int So, int planes, int inverse, int32_t out[10]) {
+  if (out == nullptr) return FH_EINVAL;
+  memset(out, 0, sizeof(int32_t) * 10);
+  if (!dct_rect_sizes_ok(S, So, planes)) return FH_EINVAL;
+  int shp[2][3];
+  dct_rect_shapes(S, So, inverse != 0, shp);
+  for (int i = 0; i < 2; ++i) {
+    const dct_rect_plan_t pn = dct_rect_plan(shp[i][0], shp[i][1], shp[i][2], planes);
+    if (pn.lds_bytes > kLdsRect) {
+      memset(out, 0, sizeof(int32_t) * 10);
+      return FH_ESIZE;
+    }
+    out[5 * i] = pn.gx, out[5 * i + 1] = pn.gy, out[5 * i + 2] = pn.gz, out[5 * i + 3] = 256, out[5 * i + 4] = (int32_t)pn.lds_bytes;
+  }
+  return 0;
+}
+
+int fh_dct_rect(fh_context* ctx, const double* in, double* out, const double* P_w, const double* P_h, int So, int planes,
+                int inverse, void* stream) {
+  if (!ctx || !in || !out || !P_w || !P_h) return FH_EINVAL;
+  return dct_rect_launch(ctx, in, out, planes, P_w, P_h, So, inverse != 0, nullptr, 0.0, nullptr, (hipStream_t)stream);
 }
 
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream) {
@@ -3363,7 +3603,7 @@ int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double*
 
 int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, void* stream) {
   if (!ctx || !p || !u || !out) return FH_EINVAL;
-  if (problem_check(p)) return FH_EINVAL;
+  if (problem_check(p, ctx->S)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)u | (uintptr_t)out) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const fh_batch per = batch_of(p);
   if (masks_check(p, per)) return FH_EINVAL;
@@ -3469,9 +3709,9 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (nimg < 1 || nimg > ctx->nimg_max || nimg > FH_MAX_BATCH) return FH_ESIZE;
   hipStream_t st = (hipStream_t)stream;
   const int S = ctx->S;
-  if (problem_check(p) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
+  if (problem_check(p, S) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
-  const int So = S / (p->op == 2 ? p->stride : 1);
+  const int So = S / (p->op == 2 || p->op == 7 ? p->stride : 1);
   const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r

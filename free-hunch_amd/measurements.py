@@ -120,17 +120,31 @@ def folded_dct_blur_bases(col_dy, col_w, row_dx, row_w, S):
     so the four image passes of the two blurs disappear into the (dense) DCT passes.  F is circulant,
     F[i][i'] = sum_t w_t [i' = (i - d_t) mod S], hence P[k][n] = sum_t w_t C[k][(n - d_t) mod S] - formed in extended
     precision and rounded once.  Returns float64 (P_row, P_col, P_row^T, P_col^T), C-contiguous [S][S]."""
-    C = dct_basis_longdouble(S)
-
-    def fold(offsets, weights):
-        P = np.zeros((S, S), dtype=np.longdouble)
-        for d, w in zip(offsets, weights):
-            P += np.longdouble(w) * np.roll(C, int(d), axis=1)
-        return P
-
-    P_row, P_col = fold(row_dx, row_w), fold(col_dy, col_w)
+    P_row, P_col = _fold_longdouble(row_dx, row_w, S), _fold_longdouble(col_dy, col_w, S)
     f = lambda M: np.ascontiguousarray(M.astype(np.float64))
     return f(P_row), f(P_col), f(P_row.T), f(P_col.T)
+
+
+def _fold_longdouble(offsets, weights, S):
+    """P[k][n] = sum_t w_t C[k][(n - d_t) mod S] in extended precision (folded_dct_blur_bases)"""
+    C = dct_basis_longdouble(S)
+    P = np.zeros((S, S), dtype=np.longdouble)
+    for d, w in zip(offsets, weights):
+        P += np.longdouble(w) * np.roll(C, int(d), axis=1)
+    return P
+
+
+def folded_dct_sr_bases(col_dy, col_w, row_dx, row_w, S, s):
+    """`folded_dct_blur_bases` for blur + decimation by s (s divides S, So = S / s):  A(X) = Dec_s F_col X F_row^T Dec_s^T, and
+    with G[k][j] = P[k][j s] - P with every s-th column kept, [S][So] -
+        dct2(A^T u)  = G_col u G_row^T,        A(idct2(v)) = G_col^T v G_row
+    (A^T zero-inserts u, which selects those columns of P).  The extended-precision P is subsampled before the single
+    rounding.  Returns float64 (G_row, G_col, G_row^T, G_col^T), C-contiguous, [S][So] and [So][S]."""
+    if s < 1 or S % s != 0:
+        raise ValueError(f"folded_dct_sr_bases: the factor {s} does not divide the image side {S}")
+    G_row, G_col = _fold_longdouble(row_dx, row_w, S)[:, ::s], _fold_longdouble(col_dy, col_w, S)[:, ::s]
+    f = lambda M: np.ascontiguousarray(M.astype(np.float64))
+    return f(G_row), f(G_col), f(G_row.T), f(G_col.T)
 
 
 def pack_symmetric_halves(P):
@@ -209,7 +223,7 @@ class LinearOperator:
         y = getattr(self, "_last_y", None)
         FBFy = None
         if y is not None:
-            sf = getattr(self, "scale_factor", 1) if self.name == "super_resolution" else 1
+            sf = getattr(self, "scale_factor", 1) if self.name in ("super_resolution", "custom_sr") else 1
             up = torch.zeros(y.shape[0], y.shape[1], S, S, device=self.device, dtype=y.dtype)
             up[..., ::sf, ::sf] = y
             FBFy = FBC * torch.fft.fftn(up, dim=(-2, -1))
@@ -354,6 +368,84 @@ class MaskedBlurOperator(CustomBlurOperator):
     def forward_adjoint(self, v):
         """exact adjoint of the noiseless `forward`: B^T (mask * v)"""
         return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
+
+
+_SR_FOLD_CACHE = {}
+
+
+@register_operator(name="custom_sr")
+class CustomSROperator(CustomBlurOperator):
+    """Super-resolution with the caller's own PSF and factor: y = (B x)[..., ::s, ::s] + sigma_s n, B the circular blur of
+    `custom_blur` (same PSF arguments and checks: `kernel_path` or `kernel`, used as given, centre at index size // 2),
+    s = `scale_factor`, an integer 2 .. 16 that divides the image side and leaves at least 8 x 8 measurements.  Unlike
+    `super_resolution` the measurement IS the solver's A: `forward` is blur + decimation, `transpose` its exact adjoint.
+    Every route outside the folded solve runs the PSF's tap list (k_conv_dec / k_conv_up), so the PSF has at most
+    `Taps.MAX_TAPS` non-zeros; a rank-1 PSF (box, Gaussian, binomial) additionally folds into rectangular DCT bases
+    (`folded_sr_bases`, fh_problem.op = 7)."""
+
+    def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernel_path=None, kernel=None, **kwargs):
+        s = scale_factor
+        ok = isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, bool) and float(s) == int(s)
+        if ok and int(s) == 1:
+            raise ValueError("custom_sr: scale_factor = 1 does not decimate - use custom_blur for a blur at full resolution")
+        if not ok or not 2 <= int(s) <= 16:
+            raise ValueError(f"custom_sr: scale_factor must be an integer from 2 to 16, got {scale_factor!r}")
+        s = int(s)
+        super().__init__(in_shape, sigma_s, device, kernel_path=kernel_path, kernel=kernel)
+        S = int(in_shape[-1])
+        if S % s != 0:
+            raise ValueError(f"custom_sr: scale_factor {s} does not divide the image side {S}")
+        if S // s < 8:
+            raise ValueError(f"custom_sr: scale_factor {s} leaves a {S // s} x {S // s} measurement of a {S} x {S} image; at "
+                             "least 8 x 8 is required")
+        if self.taps.n > Taps.MAX_TAPS:
+            raise ValueError(f"custom_sr: the PSF has {self.taps.n} non-zeros, a tap list holds {Taps.MAX_TAPS}; a decimating "
+                             "dense-window kernel is out of scope")
+        import ctypes
+        plan, out = _lib.load().fh_conv_circ_plan, (ctypes.c_int32 * 6)()
+        for adjoint in (0, 1):
+            rc = plan(S, self.taps.n, self.taps.halo, 3, s, adjoint, out)
+            if rc != 0:
+                raise ValueError(f"custom_sr: no kernel runs this PSF's tap list ({self.taps.n} taps reaching ({self.taps.hy}, "
+                                 f"{self.taps.hx})) at stride {s} on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
+        self.scale_factor = s
+        self.out_shape = (1, 3, S // s, S // s)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # the noise is drawn at the low-resolution shape
+        y = self._noise(self._conv(data, stride=self.scale_factor).to(data.dtype), noiseless)
+        self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.out_shape[-3:])
+        return self._conv(y, stride=self.scale_factor, adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`, for DPS"""
+        return self._conv(v, stride=self.scale_factor, adjoint=True).to(v.dtype)
+
+    def folded_bases(self):
+        return None  # (the stride-1 fold does not apply to a decimating operator)
+
+    def folded_sr_bases(self):
+        """device copies of `folded_dct_sr_bases` (G_row, G_col, G_row^T, G_col^T) for a rank-1 PSF - None when the PSF is not
+        rank-1 or FH_NO_FOLD=1; built once per (PSF, size, factor, device), shared by all instances."""
+        sep = self.taps.sep
+        if sep is None or os.environ.get("FH_NO_FOLD") == "1":
+            return None
+        S, s = self.in_shape[-1], self.scale_factor
+        col, row = sep
+        key = (S, s, str(self.device), col.dy.cpu().numpy().tobytes(), col.w.cpu().numpy().tobytes(),
+               row.dx.cpu().numpy().tobytes(), row.w.cpu().numpy().tobytes())
+        if key not in _SR_FOLD_CACHE:
+            mats = folded_dct_sr_bases(col.dy.cpu().numpy(), col.w.cpu().numpy(), row.dx.cpu().numpy(), row.w.cpu().numpy(),
+                                       S, s)
+            _SR_FOLD_CACHE[key] = tuple(torch.from_numpy(m).to(self.device) for m in mats)
+        return _SR_FOLD_CACHE[key]
 
 
 def _cubic(x):

@@ -64,6 +64,19 @@ int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inv
  * arithmetic only: needs no context and no device. */
 int fh_dct_sym_plan(int S, int planes, int* gx, int* gy, int* gz, int* ns, int64_t* lds_bytes);
 
+/* Two rectangular dense passes over `planes` planes at the context's side S and a second side So (1 <= So <= S):
+ *   inverse = 0:  out[planes][S][S]   = P_h in P_w^T,  in [planes][So][So], P_w and P_h [S][So]
+ *   inverse = 1:  out[planes][So][So] = P_h in P_w^T,  in [planes][S][S],   P_w and P_h [So][S]
+ * all float64, row-major.  With the bases of fh_problem.op = 7 this is dct2(A^T u) / A(idct2(v)) of blur + decimation by S / So;
+ * with So = S and the DCT basis it is fh_dct2d.  Every output is one chain of multiply-adds with the summation index ascending,
+ * whatever `planes`.  in may equal out.  FH_EINVAL: a null pointer, So or planes out of range; FH_ESIZE: planes beyond the
+ * context's planes_max.
+ * fh_dct_rect_plan reports the two launches without a context or a device (S even, 2 .. 256, as fh_context_create):
+ * out = {grid x, grid y, grid z, block size, dynamic LDS bytes} of pass A (along W), then of pass B (zeros on an error). */
+int fh_dct_rect(fh_context* ctx, const double* in, double* out, const double* P_w, const double* P_h, int So, int planes,
+                int inverse, void* stream);
+int fh_dct_rect_plan(int S, int So, int planes, int inverse, int32_t out[10]);
+
 /* Adds the DCT moments of n images to running sums: the accumulation loop of the DCT-variance prior,
  * do_frequency_analysis.py:40-44.  imgs: uint8 [n][3][S][S] (4-byte aligned); work: n*3*S*S doubles of scratch;
  * sum, sumsq: double [3][S][S], read and written (16-byte aligned, zeroed by the caller before the first call).
@@ -234,6 +247,12 @@ typedef struct fh_problem {
    * An all-ones mask gives the bits of op = 1.  6 masked dense-window blur: the same with B the window of op = 4 - every field as
    * for op = 4 and every refusal of op = 4, plus mask != NULL; an all-ones mask gives the bits of op = 4.  A null mask or
    * stride != 1: FH_EINVAL before any launch.
+   * 7 separable super-resolution on folded rectangular bases: A(X) = (F_col X F_row^T)[::s, ::s] with a rank-1 PSF, s = stride >= 2
+   * a divisor of S, So = S / s.  With P = C_dct F^T and G[k][j] = P[k][j s] ([S][So]):  fold_fwd_w = G_row, fold_fwd_h = G_col
+   * (dct2(A^T u) = G_col u G_row^T), fold_inv_w = G_row^T, fold_inv_h = G_col^T ([So][S]; A(idct2(v)) = G_col^T v G_row), all four
+   * non-null, use_dct = 1, fold_sym = 0, mask null (per->mask[i] null); the tap fields are ignored.  The measurement - u, b, x - is
+   * [3][So][So] per image, as for op = 2.  Anything else: FH_EINVAL before any launch.  free-hunch_amd/measurements.py:
+   * folded_dct_sr_bases.  The same operator with its tap list is op = 2.
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
