@@ -64,14 +64,19 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 
 # fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
 # (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
-# into rectangular DCT bases op = 7, see _problem)
+# into rectangular DCT bases op = 7, see _problem; a weighted_blur on the dense-window kernel is op = 9, a weighted_sr on the
+# rectangular bases op = 11)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
-            "noise": 0, "masked_blur": 5, "custom_sr": 2}
+            "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
-_SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr")  # operators whose PSF is the caller's: a lock-step batch must share it
-_DECIMATING = ("super_resolution", "custom_sr")  # operators with a scale_factor: A = blur + decimation on the PSF's tap list
+# operators whose PSF is the caller's: a lock-step batch must share it
+_SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr")
+# operators with a scale_factor: A = blur + decimation on the PSF's tap list
+_DECIMATING = ("super_resolution", "custom_sr", "weighted_sr")
+# operators with a per-pixel noise map: the solver whitens with operator.weights = 1 / sigma_i and sigma_y2 = 1 (ops 8 .. 11)
+_WEIGHTED = ("weighted_blur", "weighted_sr")
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', 'noise', 'custom_blur', 'masked_blur', or 'custom_sr'.")
+                 "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -103,9 +108,9 @@ def _problem(operator, cov, sigma_y2):
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
         p.ntaps, p.tap_w = 3, w.data_ptr()
         keep.append(w)
-    elif p.op in (1, 5) and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
+    elif p.op in (1, 5, 8) and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
         win, hy, hx = operator.taps.window
-        p.op, p.ntaps, p.halo, p.tap_w = (4 if p.op == 1 else 6), win.numel(), 64 * hy + hx, win.data_ptr()
+        p.op, p.ntaps, p.halo, p.tap_w = {1: 4, 5: 6, 8: 9}[p.op], win.numel(), 64 * hy + hx, win.data_ptr()
         keep.append(win)
     else:
         t = operator.taps
@@ -115,22 +120,32 @@ def _problem(operator, cov, sigma_y2):
             p.tap2_dy, p.tap2_dx, p.tap2_w = t2.dy.data_ptr(), t2.dx.data_ptr(), t2.w.data_ptr()
         p.ntaps, p.halo = t.n, t.halo
         p.tap_dy, p.tap_dx, p.tap_w = t.dy.data_ptr(), t.dx.data_ptr(), t.w.data_ptr()
-        fold = operator.folded_bases() if (cov.use_dct and p.op in (1, 5)) else None
+        fold = operator.folded_bases() if (cov.use_dct and p.op in (1, 5, 8)) else None
         if fold is not None:  # separable blur absorbed by the DCT passes of A C A^T (measurements.folded_dct_blur_bases)
             mats, sym = fold
             p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in mats)
             p.fold_sym = int(sym)
             keep.extend(mats)
-        sr = operator.folded_sr_bases() if (cov.use_dct and operator.name == "custom_sr") else None
+        sr = operator.folded_sr_bases() if (cov.use_dct and operator.name in ("custom_sr", "weighted_sr")) else None
         if sr is not None:  # rank-1 PSF + decimation absorbed by rectangular DCT bases (measurements.folded_dct_sr_bases)
-            p.op = 7
+            p.op = 7 if p.op == 2 else 11
             p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in sr)
             keep.extend(sr)
     if operator.name == "masked_blur":  # A = M B: the mask rides with the blur's fields (ops 5 / 6); kept LAST in `keep`
         mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
         p.mask = mask.data_ptr()
         keep.append(mask)
+    if operator.name in _WEIGHTED:  # the weights 1 / sigma_i ride in the mask field (ops 8 .. 11); kept LAST in `keep`
+        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
+        p.mask = w.data_ptr()
+        keep.append(w)
     return p, keep
+
+
+def _solver_sigma_y2(operator):
+    """sigma_y2 of the system the device solves: `_sigma_y2`, or 1 for the whitened system of a noise-map operator (its
+    `sigma_s` is not read)"""
+    return 1.0 if operator.name in _WEIGHTED else _sigma_y2(operator)
 
 
 def _sigma_y2(operator):
@@ -153,7 +168,7 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     name = operator.name
     if name not in _OP_CODE:
         raise ValueError(_BAD_OPERATOR)
-    prob, keep = _problem(operator, cov, _sigma_y2(operator))
+    prob, keep = _problem(operator, cov, _solver_sigma_y2(operator))
     prob.cg_scipy = int(bool(scipy_cg))
     y64 = y.detach().to(device=dev, dtype=F64).contiguous()
     x64 = x0_mean.detach().to(device=dev, dtype=F64).contiguous()
@@ -167,7 +182,7 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     else:
         ax = operator._conv(x64, stride=prob.stride)
         b = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur":  # b = M (y - B x0)
+        if name == "masked_blur" or name in _WEIGHTED:  # b = M (y - B x0); noise map: the whitened b = W (y - A0 x0)
             b = (keep[-1].view_as(b) * b).contiguous()
     sol = torch.empty_like(b)
     info = _lib.FhCgInfo()
@@ -186,6 +201,8 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
         return sol
     if name == "colorization":
         return operator._mix(sol, adjoint=True)
+    if name in _WEIGHTED:  # mat = A0^T W u
+        sol = (keep[-1].view_as(sol) * sol).contiguous()
     return operator._conv(sol, stride=prob.stride, adjoint=True)
 
 
@@ -209,7 +226,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     # `exclusive`: nothing else synchronises across workgroups on this GPU while the solve runs (the lock-step sampler
     # has joined its per-image streams) -> the covariance apply inside CG reads each factor base once, not twice
     ctx.set_exclusive(exclusive)
-    prob, keep = _problem(op0, cov0, _sigma_y2(op0))
+    prob, keep = _problem(op0, cov0, _solver_sigma_y2(op0))
     per = _lib.FhBatch()
     per.nimg = B
     m = cov0.famC.m
@@ -226,6 +243,10 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             assert op.scale_factor == op0.scale_factor, "lock-step images must share the scale_factor"
         if name in _MASKED or name == "masked_blur":
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
+            keep.append(mk)
+            per.mask[b] = mk.data_ptr()
+        if name in _WEIGHTED:  # every image brings its own noise map
+            mk = op.weights.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
             per.mask[b] = mk.data_ptr()
     y64 = torch.cat([y.detach().to(device=dev, dtype=F64) for y in ys], 0).contiguous()
@@ -252,8 +273,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     else:
         ax = conv(x64, False)
         b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur":  # b = M (y - B x0), each image with its own mask
-            b_vec = (torch.cat([k.view(1, 3, S, S) for k in keep[-B:]], 0) * b_vec).contiguous()
+        if name == "masked_blur" or name in _WEIGHTED:  # b = M (y - B x0) / W (y - A0 x0), each image with its own map
+            b_vec = (torch.cat([k.view(1, *b_vec.shape[1:]) for k in keep[-B:]], 0) * b_vec).contiguous()
     sol = torch.empty_like(b_vec)
     rtol = rtol_func(sigma_t, max_rtol)
     rtols = (C.c_double * B)(*([rtol] * B))
@@ -268,6 +289,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
                               "residual_norm": infos[b].residual_norm, "rtol": rtol})
     if name in _MASKED:
         return sol
+    if name in _WEIGHTED:  # mat = A0^T W u
+        sol = (torch.cat([k.view(1, *sol.shape[1:]) for k in keep[-B:]], 0) * sol).contiguous()
     return mix(sol, True) if name == "colorization" else conv(sol, True)
 
 

@@ -52,6 +52,12 @@ SCHEMA = {
     # NEW: the validity mask of --operator_name=masked_blur (y = M (B x + n), the PSF from --kernel_path): a 0/1 .npy of shape
     # [S,S], [3,S,S] or [1,3,S,S], and / or a border of N dropped pixels on every side (-1: the PSF's reach); the two multiply
     "mask_path": (str, ""), "mask_border": (int, 0),
+    # NEW: the per-pixel noise level of --operator_name=weighted_blur / weighted_sr (the PSF from --kernel_path, the factor from
+    # --scale_factor): either --noise_map_path, a .npy of standard deviations in the [-1, 1] units of the measurement ([n,n],
+    # [3,n,n] or [1,3,n,n] at the measurement's side; +inf = pixel not measured), or a Poisson-Gaussian sensor --noise_gain=G
+    # --noise_read_sigma=R in intensity units of [0, 1] (measurements.poisson_gaussian_sigma): the run then synthesises the
+    # measurement with that noise and hands the solver the map estimated from the measurement
+    "noise_map_path": (str, ""), "noise_gain": (float, None), "noise_read_sigma": (float, None),
 }
 
 
@@ -87,10 +93,25 @@ def load_config(argv=None):
                              "mask use --operator_name=custom_blur)")
     if cfg["operator_name"] == "custom_sr" and not cfg["kernel_path"]:
         raise SystemExit("--operator_name=custom_sr needs --kernel_path=FILE.npy (the PSF, a 2-D array) beside --scale_factor")
+    weighted = cfg["operator_name"] in ("weighted_blur", "weighted_sr")
+    sensor = cfg["noise_gain"] is not None or cfg["noise_read_sigma"] is not None
+    if weighted:
+        if not cfg["kernel_path"]:
+            raise SystemExit(f"--operator_name={cfg['operator_name']} needs --kernel_path=FILE.npy (the PSF, a 2-D array)")
+        if sensor and (cfg["noise_gain"] is None or cfg["noise_read_sigma"] is None):
+            raise SystemExit("--noise_gain and --noise_read_sigma go together: the Poisson-Gaussian noise map needs both")
+        if bool(cfg["noise_map_path"]) == sensor:
+            raise SystemExit(f"--operator_name={cfg['operator_name']} needs a noise map: either --noise_map_path=FILE.npy or "
+                             "--noise_gain=G --noise_read_sigma=R, not both")
+    elif cfg["noise_map_path"] or sensor:
+        raise SystemExit(f"--noise_map_path, --noise_gain and --noise_read_sigma belong to --operator_name=weighted_blur / "
+                         f"weighted_sr; operator '{cfg['operator_name']}' does not read them")
     if cfg["operator_name"] != "masked_blur" and (cfg["mask_path"] or cfg["mask_border"] != 0):
         raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
-    if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr"):
-        raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr; operator "
+    if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr", "weighted_blur",
+                                                           "weighted_sr"):
+        raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr / weighted_blur / "
+                         f"weighted_sr; operator "
                          f"'{cfg['operator_name']}' does not read it")
     return SimpleNamespace(**cfg)

@@ -70,6 +70,7 @@ struct fh_context {
   // CG work vectors (n <= planes_max*S*S)
   double *cg_r, *cg_p, *cg_ap, *w0, *w1, *w2;
   double* deff;       // [nimg_max][S][S] colorization, no factor columns: D_eff = sum_c w_c^2 D_c per image (per solve; allocated by the first such solve)
+  double* cg_wp;      // [nimg_max][3][S][S] noise-map solves (fh_problem.op 8 .. 11): W p beside cg_p, the operator's input (allocated by the first such solve)
   fh_cg_state* cg_state;
   fh_cg_state* h_state;  // pinned host mirror of cg_state (read back every few iterations)
   double* h_scal;        // pinned host staging for fh_read_scalars (64 doubles)

@@ -2501,20 +2501,22 @@ static int conv_launch(fh_context* ctx, const double* in, double* out, const int
                        const double* w, int ntaps, int halo, int planes, int stride, int adjoint, const double* add,
                        double add_scale, const fh_cg_state* done, hipStream_t st, const fh_batch* masks = nullptr,
                        double* spare = nullptr) {
-  // masks (ops 5 / 6, the pass that finishes B w): out = add_scale * add + mask .* conv(in).  k_conv1d and k_conv_tile8 do
-  // it in their epilogue; the other kernels write conv(in) to `spare` (a work vector of the caller's, not in / out / add)
-  // and k_mask finishes: one more streaming pass, the same bits
+  // masks (ops 5 / 6 and the weights of ops 8 / 9 / 10, the pass that finishes B w): out = add_scale * add + mask .* conv(in).
+  // k_conv1d and k_conv_tile8 do it in their epilogue; the other kernels - every decimating pass of op 10 among them - write
+  // conv(in) to `spare` (a work vector of the caller's, not in / out / add) and k_mask finishes: one more streaming pass, the
+  // same bits.  Behind a decimating pass (adjoint = 0) the table is [3][S / stride][S / stride] per image.
   const int S = ctx->S;
   conv_choice c;
   const int rc = conv_plan_halo(S, ntaps, halo, planes, stride, adjoint, &c);
   if (rc) return rc;
   const dim3 b(256);
   if (masks != nullptr) {
-    if (stride != 1 || spare == nullptr || planes != 3 * masks->nimg) return FH_EINVAL;
+    if ((stride != 1 && adjoint) || spare == nullptr || planes != 3 * masks->nimg) return FH_EINVAL;
+    const int So = S / stride;
     fh_diag_tab mk;
     memset(&mk, 0, sizeof(mk));
     for (int i = 0; i < masks->nimg && i < FH_MAX_BATCH; ++i) mk.D[i] = masks->mask[i];
-    switch (c.kernel) {
+    switch (stride == 1 ? c.kernel : (int)kConvDirect) {
       case kConv1dCol: hipLaunchKernelGGL(k_conv1d_masked<0>, c.grid, b, c.lds, st, in, out, dy, w, ntaps, S, c.h, adjoint, add, add_scale, done, mk); break;
       case kConv1dRow: hipLaunchKernelGGL(k_conv1d_masked<1>, c.grid, b, c.lds, st, in, out, dx, w, ntaps, S, c.h, adjoint, add, add_scale, done, mk); break;
       case kConvTile8: hipLaunchKernelGGL(k_conv_tile8_masked, c.grid, b, c.lds, st, in, out, dy, dx, w, ntaps, S, c.hy, c.hx, adjoint, add, add_scale, done, mk); break;
@@ -2522,7 +2524,7 @@ static int conv_launch(fh_context* ctx, const double* in, double* out, const int
         const int rc2 = conv_launch(ctx, in, spare, dy, dx, w, ntaps, halo, planes, stride, adjoint, nullptr, 0.0, done, st);
         if (rc2) return rc2;
         hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)masks->nimg), b, 0, st, *masks, (const double*)spare, add, add_scale,
-                           out, (int64_t)3 * S * S, done);
+                           out, (int64_t)3 * So * So, done);
       }
     }
     FH_LAUNCH_CHECK();
@@ -2585,25 +2587,32 @@ static int window_problem_check(const fh_problem* p) {
 // (the masks of a batched solve are per->mask[i]: masks_check)
 // S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 7) return FH_EINVAL;
-  if (p->op == 7) {  // separable SR on folded rectangular bases: the four [S][S / stride] / [S / stride][S] bases, no mask
-    if (p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0 || p->mask != nullptr) return FH_EINVAL;
+  if (p->op < 0 || p->op > 11) return FH_EINVAL;
+  if (p->op == 7 || p->op == 11) {  // separable SR on folded rectangular bases: the four [S][S / stride] / [S / stride][S] bases
+    if (p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0) return FH_EINVAL;
+    if (p->op == 7 && p->mask != nullptr) return FH_EINVAL;  // no mask on the low-resolution measurement (the weights: op 11)
     if (!p->fold_fwd_w || !p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
     return 0;
   }
+  if (p->op == 10) return p->stride < 2 || S % p->stride != 0 ? FH_EINVAL : 0;  // the tap list of op 2 at a true decimation
   if (p->op >= 5 && p->stride != 1) return FH_EINVAL;
-  return p->op == 4 || p->op == 6 ? window_problem_check(p) : 0;
+  return p->op == 4 || p->op == 6 || p->op == 9 ? window_problem_check(p) : 0;
 }
 
 // ops 5 / 6 (masked blur): every image of the batch brings a mask
 static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
+// ops 8 .. 11 (per-pixel noise map): the mask field carries the weights w = 1 / sigma, [3][n][n] per image at the
+// measurement's side n (S for ops 8 / 9, S / stride for ops 10 / 11)
+static bool weighted_op(const fh_problem* p) { return p->op >= 8 && p->op <= 11; }
+static bool decimating_op(const fh_problem* p) { return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11; }
 static int masks_check(const fh_problem* p, const fh_batch& per) {
   if (p->op == 7) {  // no mask on the low-resolution measurement
     for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
       if (per.mask[i] != nullptr) return FH_EINVAL;
     return 0;
   }
-  if (!masked_op(p)) return 0;
+  if (weighted_op(p) && p->mask == nullptr) return FH_EINVAL;
+  if (!masked_op(p) && !weighted_op(p)) return 0;
   if (per.nimg < 1 || per.nimg > FH_MAX_BATCH) return FH_EINVAL;
   for (int i = 0; i < per.nimg; ++i)
     if (per.mask[i] == nullptr) return FH_EINVAL;
@@ -2650,6 +2659,13 @@ static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch
 // supported on the mask (off the mask A_mm(v) = sigma_y^2 v + 0 * t = 0 where v = 0), p0 = r0, and every later
 // r = r - alpha A p, p = r + beta p keeps that support; M p is then the product of every entry with exactly 1 or of a zero
 // with 0 - p itself, bit for bit.  So every iterate equals the one the fully masked operator would give.
+//
+// Per-pixel noise map (ops 8 / 9 / 10 / 11: the fields of ops 1 / 4 / 2 / 7 with the weights w = 1 / sigma in per.mask): the
+// whitened system  A_mm(u) = sigma_y^2 u + W A0 C A0^T W u,  W = diag(w).  The output-side W takes the place of M above, in the
+// same expression fma(sigma_y^2, u, w * t); op 11 hands the weights to inverse pass B of k_dct_rect as its table, op 10 runs a
+// k_mask pass over the 3 So^2 measurements behind its decimating kernel.  W is not idempotent, so the input side cannot be
+// skipped: every caller hands in uin = W u - fh_amm from a k_mask pass, the CG from the direction update that writes p
+// (k_cg_init_w / k_cg_step2_w keep W p beside p).  u itself stays the add / dot operand: the partials are p . A_mm(p).
 static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* u, double* out,
                       const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr,
                       const double* uin = nullptr) {
@@ -2666,8 +2682,8 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   if (rc) return rc;
   rc = masks_check(p, per);
   if (rc) return rc;
-  const bool blur = p->op == 1 || p->op == 5, window = p->op == 4 || p->op == 6;
-  const fh_batch* masks = masked_op(p) ? &per : nullptr;
+  const bool blur = p->op == 1 || p->op == 5 || p->op == 8, window = p->op == 4 || p->op == 6 || p->op == 9;
+  const fh_batch* masks = masked_op(p) || weighted_op(p) ? &per : nullptr;
   fh_batch mdiag;  // the masks as the per-image table of k_dct_sym's epilogue (indexed by the natural output pixel)
   memset(&mdiag, 0, sizeof(mdiag));
   mdiag.nimg = nimg;
@@ -2714,21 +2730,22 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
                        0.0, states);
     return dct2d_launch(ctx, w0, out, nimg, 1, states, st, 1, u, p->sigma_y2, dot_part, kCgScratch, dot_nparts);
   }
-  if (p->op == 7) {
+  if (p->op == 7 || p->op == 11) {
     // rank-1 PSF + decimation folded into rectangular DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in four small
     // dense passes + the apply; u, out are [3][So][So] per image.  With no factor columns C z = D .* z rides in forward pass B.
+    // op 11: the first pass reads uin = W u, and inverse pass B carries the weights as its table, out = fma(sigma_y^2, u, w * t)
     const int So = S / p->stride;
     if (planes > ctx->planes_max) return FH_ESIZE;
     if (p->m == 0) {
-      rc = dct_rect_launch(ctx, u, w0, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st, &per);
+      rc = dct_rect_launch(ctx, uin, w0, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st, &per);
       if (rc) return rc;
     } else {
-      rc = dct_rect_launch(ctx, u, w1, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st);
+      rc = dct_rect_launch(ctx, uin, w1, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st);
       if (rc) return rc;
       rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
       if (rc) return rc;
     }
-    return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, So, 1, u, p->sigma_y2, states, st, nullptr,
+    return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, So, 1, u, p->sigma_y2, states, st, mtab,
                            dot_part, kCgScratch, dot_nparts);
   }
   const int halo = p->halo;
@@ -2845,14 +2862,21 @@ __device__ __forceinline__ double sum_partials(const double* __restrict__ part, 
 }
 
 // r = b - Ab ; p = r ; x = b ; partial r.r and b.b
-__global__ __launch_bounds__(256) void k_cg_init(const double* __restrict__ b, const double* __restrict__ Ab,
-                                                 double* __restrict__ x, double* __restrict__ r,
-                                                 double* __restrict__ p, double* __restrict__ part, int64_t n) {
+// WEIGHTED (here and in cg_step2_body; ops 8 .. 11): the kernel that writes the direction p also writes wp = w .* p, the input
+// of the next operator apply (amm_launch: uin), from the weights wt.D[image] ([n] per image).  A compile-time flag, as MASKED
+// in the convolution kernels: the unweighted entry points instantiate `false` and never touch wt / wp.
+template <bool WEIGHTED>
+__device__ __forceinline__ void cg_init_body(const double* __restrict__ b, const double* __restrict__ Ab,
+                                             double* __restrict__ x, double* __restrict__ r, double* __restrict__ p,
+                                             double* __restrict__ part, int64_t n, const fh_diag_tab& wt,
+                                             double* __restrict__ wp) {
+  const double* __restrict__ w = nullptr;
   {
     const int64_t off = (int64_t)blockIdx.z * n;
     b += off, x += off, r += off, p += off;
     if (Ab != nullptr) Ab += off;
     part += (int64_t)blockIdx.z * kCgScratch;
+    if (WEIGHTED) w = wt.D[blockIdx.z], wp += off;
   }
   __shared__ double red[4];
   double srr = 0.0, sbb = 0.0;
@@ -2861,6 +2885,7 @@ __global__ __launch_bounds__(256) void k_cg_init(const double* __restrict__ b, c
     x[i] = Ab != nullptr ? bi : 0.0;
     r[i] = ri;
     p[i] = ri;
+    if (WEIGHTED) wp[i] = w[i] * ri;
     srr = fma(ri, ri, srr);
     sbb = fma(bi, bi, sbb);
   }
@@ -2870,6 +2895,19 @@ __global__ __launch_bounds__(256) void k_cg_init(const double* __restrict__ b, c
     part[blockIdx.x] = srr;
     part[kDotBlocks + blockIdx.x] = sbb;
   }
+}
+
+__global__ __launch_bounds__(256) void k_cg_init(const double* __restrict__ b, const double* __restrict__ Ab,
+                                                 double* __restrict__ x, double* __restrict__ r,
+                                                 double* __restrict__ p, double* __restrict__ part, int64_t n) {
+  cg_init_body<false>(b, Ab, x, r, p, part, n, fh_diag_tab{}, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_cg_init_w(const double* __restrict__ b, const double* __restrict__ Ab,
+                                                   double* __restrict__ x, double* __restrict__ r,
+                                                   double* __restrict__ p, double* __restrict__ part, int64_t n,
+                                                   fh_diag_tab wt, double* __restrict__ wp) {
+  cg_init_body<true>(b, Ab, x, r, p, part, n, wt, wp);
 }
 
 __global__ __launch_bounds__(256) void k_cg_init_fin(const double* __restrict__ part, int nparts, RtolArr rtols,
@@ -2944,16 +2982,20 @@ __global__ __launch_bounds__(256) void k_cg_step1(const double* __restrict__ p, 
   if (blockIdx.x == 0 && threadIdx.x == 0) stt->k_cur = k;
 }
 
-// iteration k, second half: stopping test, p = r + beta p
-__global__ __launch_bounds__(256) void k_cg_step2(const double* __restrict__ r, double* __restrict__ p,
-                                                  const double* __restrict__ part_rr, int nparts,
-                                                  double* __restrict__ rzbuf, fh_cg_state* __restrict__ stt,
-                                                  int64_t n) {
+// iteration k, second half: stopping test, p = r + beta p  (WEIGHTED: and wp = w .* p, see cg_init_body; an image that is
+// done leaves wp as it leaves p)
+template <bool WEIGHTED>
+__device__ __forceinline__ void cg_step2_body(const double* __restrict__ r, double* __restrict__ p,
+                                              const double* __restrict__ part_rr, int nparts, double* __restrict__ rzbuf,
+                                              fh_cg_state* __restrict__ stt, int64_t n, const fh_diag_tab& wt,
+                                              double* __restrict__ wp) {
+  const double* __restrict__ w = nullptr;
   {
     const int64_t off = (int64_t)blockIdx.z * n, so = (int64_t)blockIdx.z * kCgScratch;
     r += off, p += off;
     part_rr += so, rzbuf += so;
     stt += blockIdx.z;
+    if (WEIGHTED) w = wt.D[blockIdx.z], wp += off;
   }
   if (stt->done) return;
   const int k = stt->k_cur;
@@ -2970,14 +3012,31 @@ __global__ __launch_bounds__(256) void k_cg_step2(const double* __restrict__ r, 
     return;
   }
   const double beta = rz_new / rzbuf[(k - 1) & 1];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    p[i] = fma(beta, p[i], r[i]);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const double pi = fma(beta, p[i], r[i]);
+    p[i] = pi;
+    if (WEIGHTED) wp[i] = w[i] * pi;
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     rzbuf[k & 1] = rz_new;
     stt->rnorm = rnorm;
     stt->niter = k;
     stt->it = k;
   }
+}
+
+__global__ __launch_bounds__(256) void k_cg_step2(const double* __restrict__ r, double* __restrict__ p,
+                                                  const double* __restrict__ part_rr, int nparts,
+                                                  double* __restrict__ rzbuf, fh_cg_state* __restrict__ stt,
+                                                  int64_t n) {
+  cg_step2_body<false>(r, p, part_rr, nparts, rzbuf, stt, n, fh_diag_tab{}, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_cg_step2_w(const double* __restrict__ r, double* __restrict__ p,
+                                                    const double* __restrict__ part_rr, int nparts,
+                                                    double* __restrict__ rzbuf, fh_cg_state* __restrict__ stt, int64_t n,
+                                                    fh_diag_tab wt, double* __restrict__ wp) {
+  cg_step2_body<true>(r, p, part_rr, nparts, rzbuf, stt, n, wt, wp);
 }
 
 // ================================================================================================
@@ -3085,7 +3144,7 @@ int fh_context_destroy(fh_context* c) {
   std::lock_guard<std::mutex> capture_lock(g_capture_mu);
   void* bufs[] = {c->basis, c->basis_t, c->tmp_img, c->partial, c->gpartial, c->coef, c->cg_r,
                   c->cg_p,  c->cg_ap,   c->w0,      c->w1,      c->w2,       c->cg_state, c->sync,
-                  c->sym_fwd, c->sym_inv, c->deff};
+                  c->sym_fwd, c->sym_inv, c->deff, c->cg_wp};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   for (auto& g : c->graphs)
@@ -3609,14 +3668,24 @@ int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, v
   if (masks_check(p, per)) return FH_EINVAL;
   const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
   if (rc) return rc;
-  if (masked_op(p)) {  // the input-side mask of A_mm (amm_launch): M u into a CG vector, which is idle outside a solve
+  if (masked_op(p) || weighted_op(p)) {
+    // the input-side mask / weights of A_mm (amm_launch): M u or W u into a CG vector, which is idle outside a solve
     if (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3) return FH_EINVAL;
     if (ctx->planes_max < 3) return FH_ESIZE;
+    const int So = ctx->S / (decimating_op(p) ? p->stride : 1);
     hipLaunchKernelGGL(k_mask, dim3(512, 1, 1), dim3(256), 0, (hipStream_t)stream, per, u, (const double*)nullptr, 0.0, ctx->cg_p,
-                       p->d, (const fh_cg_state*)nullptr);
+                       (int64_t)3 * So * So, (const fh_cg_state*)nullptr);
     return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, ctx->cg_p);
   }
   return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
+}
+
+// the weights of ops 8 .. 11 as the per-image table of k_cg_init_w / k_cg_step2_w
+static fh_diag_tab weights_tab(const fh_batch& per) {
+  fh_diag_tab wt;
+  memset(&wt, 0, sizeof(wt));
+  for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i) wt.D[i] = per.mask[i];
+  return wt;
 }
 
 // One chunk of CG iterations for all images of the batch, enqueued on `st` (eagerly, or while the stream is being
@@ -3628,9 +3697,11 @@ static int cg_enqueue_chunk(fh_context* ctx, const fh_problem* p, const fh_batch
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;
   fh_cg_state* stt = ctx->cg_state;
   const dim3 grid(kCgBlocks, 1, (unsigned)per.nimg);
+  const bool weighted = weighted_op(p);  // the operator reads W p, which k_cg_step2_w leaves in cg_wp beside p
+  const fh_diag_tab wt = weights_tab(per);
   for (int i = 0; i < count; ++i) {
     int dot_n = 0;  // > 0: the operator's last pass already left the p.Ap block partials
-    int rc = amm_launch(ctx, p, per, pk, ap, stt, st, part, &dot_n);
+    int rc = amm_launch(ctx, p, per, pk, ap, stt, st, part, &dot_n, weighted ? ctx->cg_wp : nullptr);
     if (rc) return rc;
     if (dot_n == 0) {
       hipLaunchKernelGGL(k_dot_partial, grid, dim3(256), 0, st, (const double*)pk, (const double*)ap,
@@ -3639,8 +3710,12 @@ static int cg_enqueue_chunk(fh_context* ctx, const fh_problem* p, const fh_batch
     }
     hipLaunchKernelGGL(k_cg_step1, grid, dim3(256), 0, st, (const double*)pk, (const double*)ap, x, r,
                        (const double*)part, dot_n, part + 2 * kDotBlocks, (const double*)rzbuf, stt, n);
-    hipLaunchKernelGGL(k_cg_step2, grid, dim3(256), 0, st, (const double*)r, pk,
-                       (const double*)(part + 2 * kDotBlocks), kCgBlocks, rzbuf, stt, n);
+    if (weighted)
+      hipLaunchKernelGGL(k_cg_step2_w, grid, dim3(256), 0, st, (const double*)r, pk, (const double*)(part + 2 * kDotBlocks),
+                         kCgBlocks, rzbuf, stt, n, wt, ctx->cg_wp);
+    else
+      hipLaunchKernelGGL(k_cg_step2, grid, dim3(256), 0, st, (const double*)r, pk,
+                         (const double*)(part + 2 * kDotBlocks), kCgBlocks, rzbuf, stt, n);
   }
   return 0;
 }
@@ -3711,7 +3786,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   const int S = ctx->S;
   if (problem_check(p, S) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
-  const int So = S / (p->op == 2 || p->op == 7 ? p->stride : 1);
+  const int So = S / (decimating_op(p) ? p->stride : 1);
   const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r
@@ -3737,13 +3812,32 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
     hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->w0, n,
                        (const fh_cg_state*)nullptr);
     b = ctx->w0;
+  } else if (weighted_op(p)) {
+    // noise map: b is the caller's whitened right-hand side and is solved for as given.  W p of every iteration lives in one
+    // more CG vector, allocated by the first such solve of this context (under the capture lock, as colorize_prepare's
+    // scratch; never inside a capture); W b for the x0 = b apply comes from one k_mask pass
+    if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
+    if (ctx->cg_wp == nullptr) {
+      std::lock_guard<std::mutex> capture_lock(g_capture_mu);
+      FH_CHECK(hipMalloc(&ctx->cg_wp, sizeof(double) * ctx->nimg_max * 3 * S * S));
+    }
+    if (!p->cg_scipy) {
+      hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->cg_wp,
+                         n, (const fh_cg_state*)nullptr);
+      rc = amm_launch(ctx, p, per, b, ap, nullptr, st, nullptr, nullptr, ctx->cg_wp);
+      if (rc) return rc;
+    }
   } else if (!p->cg_scipy) {
     rc = amm_launch(ctx, p, per, b, ap, nullptr, st);  // A x0 with x0 = b
     if (rc) return rc;
   }
   const dim3 grid(kCgBlocks, 1, (unsigned)nimg);
-  hipLaunchKernelGGL(k_cg_init, grid, dim3(256), 0, st, b, p->cg_scipy ? (const double*)nullptr : (const double*)ap, ctx->cg_x,
-                     r, pk, part, n);
+  if (weighted_op(p))
+    hipLaunchKernelGGL(k_cg_init_w, grid, dim3(256), 0, st, b, p->cg_scipy ? (const double*)nullptr : (const double*)ap,
+                       ctx->cg_x, r, pk, part, n, weights_tab(per), ctx->cg_wp);
+  else
+    hipLaunchKernelGGL(k_cg_init, grid, dim3(256), 0, st, b, p->cg_scipy ? (const double*)nullptr : (const double*)ap, ctx->cg_x,
+                       r, pk, part, n);
   hipLaunchKernelGGL(k_cg_init_fin, dim3(1, 1, (unsigned)nimg), dim3(256), 0, st, (const double*)part, kCgBlocks, rt,
                      atol, maxiter, stt, rzbuf, (int)p->cg_scipy);
   const int chunk = 8;

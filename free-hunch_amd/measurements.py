@@ -223,7 +223,7 @@ class LinearOperator:
         y = getattr(self, "_last_y", None)
         FBFy = None
         if y is not None:
-            sf = getattr(self, "scale_factor", 1) if self.name in ("super_resolution", "custom_sr") else 1
+            sf = getattr(self, "scale_factor", 1) if self.name in ("super_resolution", "custom_sr", "weighted_sr") else 1
             up = torch.zeros(y.shape[0], y.shape[1], S, S, device=self.device, dtype=y.dtype)
             up[..., ::sf, ::sf] = y
             FBFy = FBC * torch.fft.fftn(up, dim=(-2, -1))
@@ -446,6 +446,107 @@ class CustomSROperator(CustomBlurOperator):
                                        S, s)
             _SR_FOLD_CACHE[key] = tuple(torch.from_numpy(m).to(self.device) for m in mats)
         return _SR_FOLD_CACHE[key]
+
+
+def poisson_gaussian_sigma(y, gain, read_sigma):
+    """Plug-in noise map of a Poisson-Gaussian sensor, sigma = 2 sqrt(gain clip((y + 1) / 2, 0, 1) + read_sigma^2): `y` in the
+    [-1, 1] units of the measurements (array or tensor), `gain` and `read_sigma` in intensity units of [0, 1]; the factor 2 maps
+    the standard deviation back to [-1, 1].  Evaluated on the measurement itself, it is what a user with real data would pass
+    as `noise_map`."""
+    gain, read_sigma = float(gain), float(read_sigma)
+    if not (np.isfinite(gain) and np.isfinite(read_sigma) and gain >= 0 and read_sigma >= 0 and gain + read_sigma > 0):
+        raise ValueError(f"poisson_gaussian_sigma: gain and read_sigma are finite and >= 0, and not both 0; got {gain}, {read_sigma}")
+    if torch.is_tensor(y):
+        return 2.0 * torch.sqrt(gain * ((y + 1.0) / 2.0).clamp(0.0, 1.0) + read_sigma ** 2)
+    return 2.0 * np.sqrt(gain * np.clip((np.asarray(y, dtype=np.float64) + 1.0) / 2.0, 0.0, 1.0) + read_sigma ** 2)
+
+
+class _NoiseMap:
+    """What `weighted_blur` and `weighted_sr` add to their parents: a per-pixel noise level, y = A0 x + n with
+    n_i ~ N(0, sigma_i^2) independent, sigma_i in (0, inf], inf = pixel not measured.
+      noise_map       array / tensor [n,n], [3,n,n] or [1,3,n,n] at the measurement's side n, in the [-1, 1] units of y; entries
+                      > 0 or +inf, not all inf
+      noise_map_path  a .npy of the same shapes (instead of `noise_map`)
+    Finite entries are clipped from below like the scalar noise level (`_sigma_y2`: 0.001, decimating operators 0.01).
+    `noise_map` is float64 [1,3,n,n] on the device, `weights` = 1 / noise_map (0 where inf) what the solver whitens with
+    (fh_problem.op 8 .. 11), `mask` = weights > 0.  `sigma_s` is accepted and stored like the parent's, but the solver does not
+    read it for these operators.  The adjoint stays unweighted - `transpose` and `forward_adjoint` are A0^T (mask * v) - so DPS
+    and DiffPIR treat the operator as they treat `masked_blur`."""
+    _NOISE_FLOOR = 0.001
+
+    def _set_noise_map(self, n, noise_map, noise_map_path):
+        name = self.name
+        noise_map_path = noise_map_path or None
+        if (noise_map is None) == (noise_map_path is None):
+            raise ValueError(f"{name} needs exactly one of noise_map (an array) and noise_map_path (a .npy file)")
+        a = np.load(noise_map_path) if noise_map is None else \
+            (noise_map.detach().cpu().numpy() if torch.is_tensor(noise_map) else np.asarray(noise_map))
+        if tuple(a.shape) not in ((n, n), (3, n, n), (1, 3, n, n)):
+            raise ValueError(f"{name}: the noise map must have shape ({n}, {n}), (3, {n}, {n}) or (1, 3, {n}, {n}), got "
+                             f"{tuple(a.shape)}")
+        a = np.asarray(a, dtype=np.float64)
+        if np.isnan(a).any():
+            raise ValueError(f"{name}: the noise map has a NaN entry")
+        if not (a > 0).all():
+            raise ValueError(f"{name}: the noise map has an entry <= 0 (entries are standard deviations > 0, or +inf for a "
+                             "pixel that was not measured)")
+        if np.isinf(a).all():
+            raise ValueError(f"{name}: the noise map is all inf - no pixel is measured")
+        s = np.ones((1, 3, n, n)) * a.reshape((1, 1, n, n) if a.ndim == 2 else (1, 3, n, n))
+        s = np.where(np.isinf(s), s, np.maximum(s, self._NOISE_FLOOR))
+        w = np.where(np.isinf(s), 0.0, 1.0 / s)
+        self.noise_map = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)  # float64 [1,3,n,n]
+        self.weights = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
+        self.mask = (self.weights > 0).to(F64)
+
+    def _noise(self, y, noiseless):
+        # one draw at the measurement shape (the parent's RNG consumption), scaled per pixel; unmeasured pixels read 0
+        keep = self.mask.to(y.dtype)
+        if not noiseless:
+            sig = torch.where(self.mask > 0, self.noise_map, torch.zeros_like(self.noise_map)).to(y.dtype)
+            y = y + sig * torch.randn_like(y)
+        return y * keep
+
+
+@register_operator(name="weighted_blur")
+class WeightedBlurOperator(_NoiseMap, CustomBlurOperator):
+    """`custom_blur` (same PSF arguments, checks and kernels) with a per-pixel noise map at the image's side, see `_NoiseMap`.
+    With the 1 x 1 PSF [[1]] it is heteroscedastic denoising."""
+
+    def __init__(self, in_shape, sigma_s, device, kernel_path=None, kernel=None, noise_map=None, noise_map_path=None, **kwargs):
+        CustomBlurOperator.__init__(self, in_shape, sigma_s, device, kernel_path=kernel_path, kernel=kernel)
+        self._set_noise_map(int(in_shape[-1]), noise_map, noise_map_path)
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.in_shape[-3:])
+        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`: A0^T (mask * v)"""
+        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
+
+
+@register_operator(name="weighted_sr")
+class WeightedSROperator(_NoiseMap, CustomSROperator):
+    """`custom_sr` (same PSF and factor arguments, checks and routes) with a per-pixel noise map at the LOW-resolution side
+    S / scale_factor, see `_NoiseMap`."""
+    _NOISE_FLOOR = 0.01
+
+    def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernel_path=None, kernel=None, noise_map=None,
+                 noise_map_path=None, **kwargs):
+        CustomSROperator.__init__(self, in_shape, sigma_s, device, scale_factor=scale_factor, kernel_path=kernel_path,
+                                  kernel=kernel)
+        self._set_noise_map(int(in_shape[-1]) // self.scale_factor, noise_map, noise_map_path)
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.out_shape[-3:])
+        return self._conv(y * self.mask.to(y.dtype), stride=self.scale_factor, adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`: A0^T (mask * v)"""
+        return self._conv(v * self.mask.to(v.dtype), stride=self.scale_factor, adjoint=True).to(v.dtype)
 
 
 def _cubic(x):

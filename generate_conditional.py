@@ -25,7 +25,7 @@ sys.path.insert(0, ROOT)
 def main(argv=None):
     from free_hunch_amd import unet as hu
     from free_hunch_amd.config import load_config
-    from free_hunch_amd.measurements import get_operator
+    from free_hunch_amd.measurements import get_operator, poisson_gaussian_sigma
     from free_hunch_amd.pipeline import gather_images, list_images, load_image_u8, lpips_u8, metrics_u8, shard_indices
     from free_hunch_amd.precond import iDDPMLinearPrecond
     from free_hunch_amd.sampler import StandardRGBEncoder, conditional_sampler, conditional_sampler_grouped
@@ -109,17 +109,30 @@ def main(argv=None):
             key = (sd * 1000003 + i) % (1 << 31)  # RNG keyed by (seed, image index): independent of the world size
             np.random.seed(key)
             torch.manual_seed(key)
-            op = get_operator(name=o.operator_name, device=device, sigma_s=o.noise_sigma, kernel_size=o.kernel_size,
-                              intensity=o.intensity, scale_factor=o.scale_factor, in_shape=(1, 3, S, S),
-                              kernel_path=o.kernel_path or None, mask_path=o.mask_path or None, mask_border=o.mask_border,
-                              mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
-                                        "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
-                                        if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})
-            op.ctx_slot = b
+            op_kw = dict(device=device, sigma_s=o.noise_sigma, kernel_size=o.kernel_size, intensity=o.intensity,
+                         scale_factor=o.scale_factor, in_shape=(1, 3, S, S), kernel_path=o.kernel_path or None,
+                         mask_path=o.mask_path or None, mask_border=o.mask_border,
+                         mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
+                                   "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
+                                   if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})
             img = load_image_u8(files[i], S)
+            x_true = enc.encode(img[None].to(device))
+            if o.operator_name in ("weighted_blur", "weighted_sr") and o.noise_gain is not None:
+                # a Poisson-Gaussian sensor: the measurement is synthesised here with the noise level of the clean signal A0 x,
+                # and the solver gets the map estimated from the measurement itself - what a user with real data would have
+                clean = get_operator(name={"weighted_blur": "custom_blur", "weighted_sr": "custom_sr"}[o.operator_name], **op_kw)
+                clean.ctx_slot = b
+                ax = clean.forward(x_true, noiseless=True)
+                y = ax + poisson_gaussian_sigma(ax, o.noise_gain, o.noise_read_sigma) * torch.randn_like(ax)
+                op = get_operator(name=o.operator_name, noise_map=poisson_gaussian_sigma(y, o.noise_gain, o.noise_read_sigma),
+                                  **op_kw)
+            else:
+                op = get_operator(name=o.operator_name, noise_map_path=o.noise_map_path or None, **op_kw)
+                y = None
+            op.ctx_slot = b
             imgs.append(img)
             ops.append(op)
-            ys.append(op.forward(enc.encode(img[None].to(device)), noiseless=False))
+            ys.append(op.forward(x_true, noiseless=False) if y is None else y)
             noise.append(torch.randn((1, 3, S, S), generator=torch.Generator().manual_seed(key), dtype=torch.float32))
         if lockstep:
             # two lock-step groups per GPU from 4 images on (the Free Hunch phase of one overlaps the UNet phase of the other:

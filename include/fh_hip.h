@@ -253,6 +253,20 @@ typedef struct fh_problem {
    * non-null, use_dct = 1, fold_sym = 0, mask null (per->mask[i] null); the tap fields are ignored.  The measurement - u, b, x - is
    * [3][So][So] per image, as for op = 2.  Anything else: FH_EINVAL before any launch.  free-hunch_amd/measurements.py:
    * folded_dct_sr_bases.  The same operator with its tap list is op = 2.
+   * 8 .. 11 per-pixel noise map: y = A0 x + n with n_i ~ N(0, sigma_i^2) independent, sigma_i in (0, inf] (inf = not measured).  The
+   * `mask` field carries the WEIGHTS w_i = 1 / sigma_i (0 where sigma_i = inf; finite, >= 0 - validated by the host, the library
+   * checks pointers only), and the library works on the whitened system with W = diag(w):
+   *   fh_amm:   A_mm(u) = sigma_y2 u + W A0 C A0^T W u for an arbitrary u (both sides are applied), = sigma_y2 u exactly where w = 0;
+   *   fh_cg_solve[_batched]: solves for b AS GIVEN - the caller passes the whitened right-hand side W (y - A0 x0) and b is not
+   *   touched; mat = A0^T W x.  The callers here pass sigma_y2 = 1.
+   * A0 and every other field are those of an existing op, with every refusal of that op:
+   *   8  = op 1 / 5 (tap list, optional second 1-D pass, optional folded bases with or without fold_sym), stride = 1;
+   *   9  = op 4 / 6 (dense window), stride = 1;                         weights and measurement vectors [3][S][S] per image
+   *   10 = op 2 (tap list), stride >= 2 a divisor of S;
+   *   11 = op 7 (rank-1 PSF folded into rectangular bases);            weights and measurement vectors [3][So][So], So = S / stride
+   * the weights of plane p at mask + (p % 3) n_plane, n_plane = S S (8 / 9) or So So (10 / 11).  mask == NULL (ops 8 .. 11, unlike
+   * op 7) or a null per->mask[i]: FH_EINVAL before any launch.  All-ones weights give the bits of ops 1 / 4 / 2 / 7, 0/1 weights with
+   * sigma_y2 = s^2 and b = M b0 those of ops 5 / 6.  The first such solve of a context allocates one more CG vector (W p).
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
@@ -267,7 +281,7 @@ typedef struct fh_problem {
   const int32_t* tap_dy; /* [ntaps] */
   const int32_t* tap_dx;
   const double* tap_w;
-  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement) */
+  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement); ops 8 .. 11: the weights */
   const double* D;       /* covariance rep: diag, row scale, base, inner matrix */
   const double* r;
   const double* B;
@@ -298,8 +312,9 @@ typedef struct fh_problem {
 } fh_problem;
 
 /* Per-image covariance pointers of a batched solve: B images share the operator, the tap lists, m, ldm and
- * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5 and 6 read
- * mask[i], which may differ from image to image (ops 5 / 6: all non-null, else FH_EINVAL; the PSF is shared). */
+ * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5, 6 and 8 .. 11 read
+ * mask[i], which may differ from image to image (ops 5 / 6 / 8 .. 11: all non-null, else FH_EINVAL; the PSF is shared; ops 8 .. 11
+ * also want a non-null fh_problem.mask). */
 #define FH_MAX_BATCH 16
 typedef struct fh_batch {
   int32_t nimg;
