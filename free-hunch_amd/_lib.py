@@ -83,6 +83,9 @@ _SIGS = {
     "fh_conv_circ": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                       C.c_void_p], C.c_int),
     "fh_conv_circ_plan": ([C.c_int] * 6 + [C.POINTER(C.c_int32)], C.c_int),
+    "fh_conv_frames": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                        C.c_void_p], C.c_int),
+    "fh_conv_frames_plan": ([C.c_int] * 7 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_conv_window": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_conv_window_plan": ([C.c_int] * 4 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_channel_mix": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
@@ -295,6 +298,14 @@ class Context:
             self.conv(x, tmp, first, planes, 1, adjoint)
             return self.conv(tmp, out, second, planes, 1, adjoint)
         return self.conv(x, out, taps, planes, stride, adjoint)
+
+    def blur_frames(self, x, out, frames, planes, stride, adjoint=False):
+        """The multi-frame SR operator pair (fh_conv_frames) of a `measurements.FrameTaps`: x [planes][S][S] -> out
+        [nimg][K][3][So][So] (frame-major), or with `adjoint` back; float64."""
+        check(self.lib.fh_conv_frames(self.h, ptr(x), ptr(out), ptr(frames.dy), ptr(frames.dx), ptr(frames.w), ptr(frames.off),
+                                      frames.nframes, frames.max_taps, frames.halo, planes, stride, int(adjoint), stream()),
+              "fh_conv_frames")
+        return out
 
     def conv(self, x, out, taps, planes, stride=1, adjoint=False):
         check(self.lib.fh_conv_circ(self.h, ptr(x), ptr(out), ptr(taps.dy), ptr(taps.dx), ptr(taps.w), taps.n,

@@ -58,6 +58,10 @@ SCHEMA = {
     # --noise_read_sigma=R in intensity units of [0, 1] (measurements.poisson_gaussian_sigma): the run then synthesises the
     # measurement with that noise and hands the solver the map estimated from the measurement
     "noise_map_path": (str, ""), "noise_gain": (float, None), "noise_read_sigma": (float, None),
+    # NEW: --operator_name=burst_sr, K low-resolution frames of one scene (K <= --scale_factor^2, factor 2 .. 4): --kernel_path holds
+    # a [K, kh, kw] array of per-frame PSFs, or one 2-D PSF that --frame_shifts="dy,dx;dy,dx;..." (K pairs, high-resolution pixels,
+    # fractions allowed) displaces per frame; with K PSFs the K shifts apply one each
+    "frame_shifts": (str, ""),
 }
 
 
@@ -93,6 +97,11 @@ def load_config(argv=None):
                              "mask use --operator_name=custom_blur)")
     if cfg["operator_name"] == "custom_sr" and not cfg["kernel_path"]:
         raise SystemExit("--operator_name=custom_sr needs --kernel_path=FILE.npy (the PSF, a 2-D array) beside --scale_factor")
+    if cfg["operator_name"] == "burst_sr" and not cfg["kernel_path"]:
+        raise SystemExit("--operator_name=burst_sr needs --kernel_path=FILE.npy (a [K, kh, kw] array of per-frame PSFs, or one 2-D "
+                         "PSF beside --frame_shifts) beside --scale_factor")
+    if cfg["frame_shifts"] and cfg["operator_name"] != "burst_sr":
+        raise SystemExit(f"--frame_shifts belongs to --operator_name=burst_sr; operator '{cfg['operator_name']}' does not read it")
     weighted = cfg["operator_name"] in ("weighted_blur", "weighted_sr")
     sensor = cfg["noise_gain"] is not None or cfg["noise_read_sigma"] is not None
     if weighted:
@@ -110,8 +119,8 @@ def load_config(argv=None):
         raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
     if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr", "weighted_blur",
-                                                           "weighted_sr"):
+                                                           "weighted_sr", "burst_sr"):
         raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr / weighted_blur / "
-                         f"weighted_sr; operator "
+                         f"weighted_sr / burst_sr; operator "
                          f"'{cfg['operator_name']}' does not read it")
     return SimpleNamespace(**cfg)

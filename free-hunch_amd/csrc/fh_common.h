@@ -49,6 +49,10 @@ struct fh_graph_entry {  // one instantiated chunk-of-iterations graph, keyed by
   fh_problem key;
   fh_batch bkey;
   int64_t n;
+  // op 12 only: the route (FH_FRAMES_FUSED) the chunk was captured on, and the checked frame offsets - the chain route slices
+  // the tap lists on the host, so the offsets BEHIND key.tap2_dy are part of what the graph holds
+  int frames_fused;
+  int32_t frame_off[17];
   hipGraphExec_t exec;
   hipGraph_t graph;
   uint64_t stamp;
@@ -82,4 +86,5 @@ struct fh_context {
   int num_cus;
   int exclusive;         // the caller guarantees that no other grid-synchronising kernel shares the GPU with this context
   int fused_disabled;    // set after a k_rep_fused time-out was reported
+  int32_t frame_off[17]; // multi-frame SR (fh_problem.op = 12, fh_conv_frames): host copy of the frame offsets, read and checked before the launches
 };

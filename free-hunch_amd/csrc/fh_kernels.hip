@@ -2119,6 +2119,165 @@ __global__ __launch_bounds__(256) void k_conv_up(const double* __restrict__ in, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Multi-frame super-resolution (fh_problem.op = 12, fh_conv_frames): K frames of one scene, A = [A_0; ..; A_{K-1}] with
+// A_k = Dec_s B_k, the tap lists of all frames concatenated and foff[K + 1] their offsets.  The measurement is frame-major,
+// [nimg][K][3][So][So]: plane (image i, channel c) of frame k is plane (i K + k) 3 + c of the low-resolution side.
+//   k_conv_dec_frames : k_conv_dec with the input tile staged ONCE, for the union of the frames' extents; the frames then take
+//                       turns in the tap staging (cap_taps pairs) and each thread runs one fma chain from 0 per frame, in list
+//                       order - the bits of K k_conv_dec / k_conv_direct launches.
+//   k_conv_up_frames  : k_conv_up per frame (low-resolution tile + phase-sorted lists re-staged, per-phase sums from 0) with the
+//                       frames' sums added in frame order into the thread's own slots of the output staging, one rounding
+//                       each - the bits of K k_conv_up launches chained through add (add_scale = 1).  One coalesced store.
+// Both read their frame's taps inside [0, ntaps) and at most cap_taps / cap of them whatever foff holds (the host has checked
+// foff before the launch, frames_prepare); the tile indices trust hy / hx like the single-frame kernels.  No atomics.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void frame_range(const int* __restrict__ foff, int k, int ntaps, int* t0, int* n) {
+  int a = foff[k], b = foff[k + 1];
+  a = a < 0 ? 0 : (a > ntaps ? ntaps : a);
+  b = b < a ? a : (b > ntaps ? ntaps : b);
+  *t0 = a, *n = b - a;
+}
+
+__global__ __launch_bounds__(256) void k_conv_dec_frames(const double* __restrict__ in, double* __restrict__ out,
+                                                         const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                         const double* __restrict__ tw, const int* __restrict__ foff,
+                                                         int K, int ntaps, int cap_taps, int S, int s, int hy, int hx,
+                                                         const double* __restrict__ add, double add_scale,
+                                                         const fh_cg_state* __restrict__ states) {
+  IMG_GUARD(states, blockIdx.z / 3);
+  extern __shared__ __align__(16) double tile[];
+  const int So = S / s;
+  const conv_dec_lds L(s, hy, hx, cap_taps);
+  const int hq = L.hq, hx4 = hq * s;
+  const int R = L.R, Wp = L.Wp;
+  double2* s_tap = reinterpret_cast<double2*>(tile + L.tap_off);
+  const int plane = blockIdx.z, oy0 = blockIdx.y * 16, ox0 = blockIdx.x * 16;
+  const double* src = in + (int64_t)plane * S * S;
+  const int gy0 = oy0 * s - hy, gx0 = ox0 * s - hx4, ncol = s * (16 + 2 * hq);
+  for (int r = threadIdx.x >> 6; r < R; r += 4) {
+    int gy = (gy0 + r) % S;
+    gy += gy < 0 ? S : 0;
+    const double* srow = src + (int64_t)gy * S;
+    for (int c = threadIdx.x & 63; c < ncol; c += 64) {
+      int gx = (gx0 + c) % S;
+      gx += gx < 0 ? S : 0;
+      tile[((c % s) * R + r) * Wp + c / s] = srow[gx];
+    }
+  }
+  const int tj = threadIdx.x & 15, ti = threadIdx.x >> 4;
+  const double* q = tile + (s * ti) * Wp + tj;
+  const int oy = oy0 + ti, ox = ox0 + tj;
+  const int img = plane / 3, ch = plane % 3;
+  for (int k = 0; k < K; ++k) {
+    int t0, n;
+    frame_range(foff, k, ntaps, &t0, &n);
+    n = n < cap_taps ? n : cap_taps;
+    if (k > 0) __syncthreads();  // the previous frame's pairs have been read
+    for (int t = threadIdx.x; t < n; t += 256) {
+      const int c = hx4 - tdx[t0 + t];  // column of the tap's operand for output column 0, >= 0
+      s_tap[t] = make_double2(tw[t0 + t], __longlong_as_double((long long)(((c % s) * R + hy - tdy[t0 + t]) * Wp + c / s)));
+    }
+    __syncthreads();  // (k = 0: the tile as well)
+    double acc = 0.0;
+#pragma unroll 4
+    for (int t = 0; t < n; ++t) {
+      const double2 tp = s_tap[t];
+      acc = fma(tp.x, q[(int)__double_as_longlong(tp.y)], acc);
+    }
+    if (oy < So && ox < So) {
+      const int64_t o = ((int64_t)(img * K + k) * 3 + ch) * So * So + (int64_t)oy * So + ox;
+      if (add != nullptr) acc = fma(add_scale, add[o], acc);
+      out[o] = acc;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_conv_up_frames(const double* __restrict__ in, double* __restrict__ out,
+                                                        const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                        const double* __restrict__ tw, const int* __restrict__ foff,
+                                                        int K, int ntaps, int S, int s, int hy, int hx, int cap,
+                                                        const fh_cg_state* __restrict__ states) {
+  IMG_GUARD(states, blockIdx.z / 3);
+  extern __shared__ __align__(16) double lds_up[];
+  const int Sin = S / s;
+  const conv_up_lds L(s, hy, hx, cap);
+  const int hqy = L.hqy, hqx = L.hqx;
+  const int Hu = L.Hu, Wu = L.Wu, T = L.T, SW = L.SW;
+  double2* lists = reinterpret_cast<double2*>(lds_up);
+  double* utile = lds_up + L.utile_off;
+  double* stage = utile + L.utile_len;
+  __shared__ int cnt_s[kUpMaxPhases];
+  const int plane = blockIdx.z, tid = threadIdx.x;
+  const int img = plane / 3, ch = plane % 3;
+  const int a0 = blockIdx.y * 16 - hqy, b0 = blockIdx.x * 16 - hqx;
+  const int la = tid >> 4, lb = tid & 15;
+  const double* q = utile + (la + hqy) * Wu + lb + hqx;
+  for (int k = 0; k < K; ++k) {
+    int t0, n_k;
+    frame_range(foff, k, ntaps, &t0, &n_k);
+    if (k > 0) __syncthreads();  // the previous frame's tile and lists have been read
+    const double* src = in + ((int64_t)(img * K + k) * 3 + ch) * Sin * Sin;
+    for (int idx = tid; idx < Hu * (Wu - 1); idx += 256) {
+      const int r = idx / (Wu - 1), c = idx % (Wu - 1);
+      int ga = (a0 + r) % Sin, gb = (b0 + c) % Sin;
+      ga += ga < 0 ? Sin : 0;
+      gb += gb < 0 ? Sin : 0;
+      utile[r * Wu + c] = src[(int64_t)ga * Sin + gb];
+    }
+    if (tid < 64) {  // one wave sorts the frame's taps by phase, keeping the list order inside every phase (as k_conv_up)
+      const int lane = tid;
+      int cnt[kUpMaxPhases];
+#pragma unroll
+      for (int p = 0; p < kUpMaxPhases; ++p) cnt[p] = 0;
+      const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+      for (int b = 0; b < n_k; b += 64) {
+        const int t = b + lane;
+        const bool valid = t < n_k;
+        const int dy = valid ? tdy[t0 + t] : 0, dx = valid ? tdx[t0 + t] : 0;
+        const int py = ((-dy) % s + s) % s, px = ((-dx) % s + s) % s;
+        const int ph = valid ? py * s + px : -1;
+        const double2 item = make_double2(valid ? tw[t0 + t] : 0.0,
+                                          __longlong_as_double((long long)(((py + dy) / s) * Wu + (px + dx) / s)));
+#pragma unroll
+        for (int p = 0; p < kUpMaxPhases; ++p) {
+          const unsigned long long mask = __ballot(ph == p);
+          if (ph == p) {
+            const int pos = cnt[p] + __popcll(mask & lt);
+            if (pos < cap) lists[p * cap + pos] = item;
+          }
+          cnt[p] += __popcll(mask);
+        }
+      }
+      if (lane < kUpMaxPhases) {
+        int c = 0;
+#pragma unroll
+        for (int p = 0; p < kUpMaxPhases; ++p) c = lane == p ? cnt[p] : c;
+        cnt_s[lane] = c < cap ? c : cap;
+      }
+    }
+    __syncthreads();
+    for (int p = 0; p < s * s; ++p) {
+      const int n = cnt_s[p];
+      const double2* lp = lists + p * cap;
+      double acc = 0.0;
+      for (int t = 0; t < n; ++t) {
+        const double2 tp = lp[t];
+        acc = fma(tp.x, q[(int)__double_as_longlong(tp.y)], acc);
+      }
+      double* slot = stage + (s * la + p / s) * SW + s * lb + p % s;  // this thread's own: no other thread touches it before the store
+      *slot = k == 0 ? acc : fma(1.0, *slot, acc);
+    }
+  }
+  __syncthreads();
+  const int oy0 = blockIdx.y * T, ox0 = blockIdx.x * T;
+  for (int idx = tid; idx < T * T; idx += 256) {
+    const int r = idx / T, c = idx % T;
+    const int oy = oy0 + r, ox = ox0 + c;
+    if (oy < S && ox < S) out[(int64_t)plane * S * S + (int64_t)oy * S + ox] = stage[r * SW + c];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The m x m part of a Woodbury step / forward time shift on the device (online_update_bfgs.py:87-119 in the real form of
 // this build):   Mdst = sym( sign * Msrc (I + alpha G Msrc)^-1 ),   (alpha, sign) = (1, -1): Woodbury inverse; (s, +1): shift.
 // One workgroup, matrices in LDS.  A = I + alpha G Msrc is NOT well conditioned: the factor columns of a trajectory are
@@ -2543,6 +2702,115 @@ static int conv_launch(fh_context* ctx, const double* in, double* out, const int
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launch plan of fh_conv_frames (fh_conv_frames_plan reports it), pure host arithmetic like conv_plan.  Two routes:
+//   fused : ONE k_conv_dec_frames / k_conv_up_frames launch over all frames and planes, where the single-frame kernel of that
+//           direction tiles the image (So % 16 == 0 forward, S % 16 s == 0 adjoint) and the LDS for the union extents - with
+//           the tap staging sized for the longest frame - fits the opt-in;
+//   chain : conv_launch per frame (and, for the frame-major layout, per image), which fixes the arithmetic: every frame's sum
+//           is one fma chain from 0 in list order, the adjoint adds the frames in index order through add (add_scale = 1).
+// The chain's plan fields describe one of its launches (3 planes, the longest frame).  Nothing here depends on the frame count.
+// ------------------------------------------------------------------------------------------------
+struct frames_choice {
+  int fused;
+  dim3 grid;
+  size_t lds;
+  int hy, hx, cap;
+};
+
+static int frames_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint,
+                       frames_choice* c) {
+  if (S < 2 || S > 256 || (S & 1) || stride < 2 || stride > 4 || S % stride != 0) return FH_EINVAL;
+  if (nframes < 1 || nframes > stride * stride || max_frame_taps < 1 || max_frame_taps > kMaxTaps) return FH_EINVAL;
+  if (planes < 3 || planes % 3 != 0 || halo < 1000 || (adjoint != 0 && adjoint != 1)) return FH_EINVAL;
+  conv_extent e;
+  int rc = conv_decode(halo, &e);
+  if (rc) return rc;
+  *c = {0, dim3(1), 0, e.hy, e.hx, 0};
+  if (planes > 65535) return FH_ESIZE;  // (the plane is grid dimension z)
+  if (!adjoint && (S / stride) % 16 == 0) {
+    c->lds = conv_dec_lds(stride, e.hy, e.hx, max_frame_taps).bytes;
+    if (c->lds <= kLdsOptIn) return c->fused = 1, c->grid = dim3(S / stride / 16, S / stride / 16, planes), 0;
+  }
+  if (adjoint && S % (16 * stride) == 0) {
+    c->cap = conv_up_lds::cap_for(stride, e.hy, e.hx);
+    c->lds = conv_up_lds(stride, e.hy, e.hx, c->cap).bytes;
+    if (c->lds <= kLdsOptIn) return c->fused = 1, c->grid = dim3(S / (16 * stride), S / (16 * stride), planes), 0;
+  }
+  conv_choice one;
+  rc = conv_plan(S, max_frame_taps, e, 3, stride, adjoint, &one);
+  if (rc) return rc;
+  c->grid = one.grid, c->lds = one.lds, c->cap = one.cap;
+  return 0;
+}
+
+// FH_FRAMES_FUSED=0: the chain also where the fused kernels fit (A/B switch, like FH_CG_NO_DOT_FUSE).  Read at every op 12
+// call (and by no other op), so one process can time both routes; the CG graph cache keys on it for op 12
+// (fh_graph_entry.frames_fused).
+static bool frames_fused_on() {
+  const char* v = getenv("FH_FRAMES_FUSED");
+  return v == nullptr || atoi(v) != 0;
+}
+
+// Host copy of the device frame offsets into ctx->frame_off (the unused tail zeroed), checked: 0 = off[0] < off[1] < .. <
+// off[K] = *ntaps, no frame longer than max_frame_taps.  *ntaps < 0 (fh_conv_frames, which is not told the total): the last
+// offset is the total, returned there.  ONE copy and one synchronisation of `st`; never inside a stream capture (fh_amm,
+// fh_conv_frames and the head of a solve).
+static int frames_prepare(fh_context* ctx, const int32_t* frame_off, int nframes, int* ntaps, int max_frame_taps, hipStream_t st) {
+  if (frame_off == nullptr || nframes < 1 || nframes > 16) return FH_EINVAL;
+  FH_CHECK(hipMemcpyAsync(ctx->h_scal, frame_off, sizeof(int32_t) * (nframes + 1), hipMemcpyDeviceToHost, st));
+  FH_CHECK(hipStreamSynchronize(st));
+  memset(ctx->frame_off, 0, sizeof(ctx->frame_off));
+  memcpy(ctx->frame_off, ctx->h_scal, sizeof(int32_t) * (nframes + 1));
+  const int32_t* o = ctx->frame_off;
+  if (*ntaps < 0) *ntaps = o[nframes];
+  if (o[0] != 0 || o[nframes] != *ntaps || *ntaps < nframes || *ntaps > nframes * max_frame_taps) return FH_EINVAL;
+  for (int k = 0; k < nframes; ++k)
+    if (o[k + 1] <= o[k] || o[k + 1] - o[k] > max_frame_taps) return FH_EINVAL;
+  return 0;
+}
+
+// in [planes][S][S] -> out [nimg][K][3][So][So] (+ add_scale * add in that layout), or with `adjoint` back (no add).
+// frames_prepare has run for these offsets.
+static int frames_launch(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
+                         const double* w, const int32_t* frame_off, int ntaps, int nframes, int max_frame_taps, int halo,
+                         int planes, int stride, int adjoint, const double* add, double add_scale, const fh_cg_state* done,
+                         hipStream_t st) {
+  const int S = ctx->S;
+  frames_choice c;
+  const int rc = frames_plan(S, nframes, max_frame_taps, halo, planes, stride, adjoint, &c);
+  if (rc) return rc;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  if (c.fused && frames_fused_on()) {
+    if (adjoint)
+      hipLaunchKernelGGL(k_conv_up_frames, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps, S, stride,
+                         c.hy, c.hx, c.cap, done);
+    else
+      hipLaunchKernelGGL(k_conv_dec_frames, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps,
+                         max_frame_taps, S, stride, c.hy, c.hx, add, add_scale, done);
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
+  const int So = S / stride;
+  const int64_t hi = (int64_t)3 * S * S, lo = (int64_t)3 * So * So;  // one image's planes at either side
+  for (int i = 0; i < planes / 3; ++i) {
+    const fh_cg_state* di = done != nullptr ? done + i : nullptr;  // (the launch carries one image: its own control block)
+    for (int k = 0; k < nframes; ++k) {
+      const int t0 = ctx->frame_off[k], n = ctx->frame_off[k + 1] - t0;
+      const int64_t f = ((int64_t)i * nframes + k) * lo;
+      int rc2;
+      if (adjoint)
+        rc2 = conv_launch(ctx, in + f, out + i * hi, dy + t0, dx + t0, w + t0, n, halo, 3, stride, 1,
+                          k > 0 ? out + i * hi : nullptr, 1.0, di, st);
+      else
+        rc2 = conv_launch(ctx, in + i * hi, out + f, dy + t0, dx + t0, w + t0, n, halo, 3, stride, 0,
+                          add != nullptr ? add + f : nullptr, add_scale, di, st);
+      if (rc2) return rc2;
+    }
+  }
+  return 0;
+}
+
 // The launch plan of fh_conv_window (fh_conv_window_plan reports it): one kernel, its grid and its LDS from conv_window_lds.
 static int window_plan(int S, int hy, int hx, int planes, dim3* grid, size_t* lds) {
   if (S < 2 || S > 256 || (S & 1) || hy < 0 || hy > 32 || hx < 0 || hx > 32 || planes < 1) return FH_EINVAL;
@@ -2587,7 +2855,16 @@ static int window_problem_check(const fh_problem* p) {
 // (the masks of a batched solve are per->mask[i]: masks_check)
 // S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 11) return FH_EINVAL;
+  if (p->op < 0 || p->op > 12) return FH_EINVAL;
+  if (p->op == 12) {  // multi-frame SR: stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
+    const int s = p->stride, K = p->ntaps2;
+    if (s < 2 || s > 4 || S % s != 0 || K < 1 || K > s * s) return FH_EINVAL;
+    if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
+    if (p->halo < 1000 || p->tap2_dy == nullptr || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
+    if (p->tap2_dx || p->tap2_w || p->mask || p->fold_sym != 0) return FH_EINVAL;
+    if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
+    return 0;
+  }
   if (p->op == 7 || p->op == 11) {  // separable SR on folded rectangular bases: the four [S][S / stride] / [S / stride][S] bases
     if (p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0) return FH_EINVAL;
     if (p->op == 7 && p->mask != nullptr) return FH_EINVAL;  // no mask on the low-resolution measurement (the weights: op 11)
@@ -2604,9 +2881,11 @@ static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
 // ops 8 .. 11 (per-pixel noise map): the mask field carries the weights w = 1 / sigma, [3][n][n] per image at the
 // measurement's side n (S for ops 8 / 9, S / stride for ops 10 / 11)
 static bool weighted_op(const fh_problem* p) { return p->op >= 8 && p->op <= 11; }
-static bool decimating_op(const fh_problem* p) { return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11; }
+static bool decimating_op(const fh_problem* p) { return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || p->op == 12; }
+// measurement planes per image: one for colorization, 3 K for the K frames of op 12, else 3
+static int meas_planes(const fh_problem* p) { return p->op == 3 ? 1 : (p->op == 12 ? p->ntaps2 : 1) * p->planes; }
 static int masks_check(const fh_problem* p, const fh_batch& per) {
-  if (p->op == 7) {  // no mask on the low-resolution measurement
+  if (p->op == 7 || p->op == 12) {  // no mask on the low-resolution measurement
     for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
       if (per.mask[i] != nullptr) return FH_EINVAL;
     return 0;
@@ -2750,7 +3029,8 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   }
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
-  const bool sep = p->ntaps2 > 0;  // separable PSF: two 1-D passes (blur only, stride 1)
+  const bool frames = p->op == 12;                // multi-frame SR: ntaps2 counts frames, tap2_dy holds their offsets
+  const bool sep = !frames && p->ntaps2 > 0;      // separable PSF: two 1-D passes (blur only, stride 1)
   if (sep && p->stride != 1) return FH_EINVAL;
   if (blur && p->use_dct && p->fold_fwd_w != nullptr) {
     // separable blur folded into the DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in 4 dense passes + the
@@ -2792,6 +3072,10 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   } else if (window) {
     rc = window_launch(ctx, uin, w0, p->tap_w, halo / 64, halo % 64, planes, 1, nullptr, 0.0, states, st);
     if (rc) return rc;
+  } else if (frames) {
+    rc = frames_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
+                       p->stride, 1, nullptr, 0.0, states, st);
+    if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, uin, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
                      states, st);
@@ -2827,6 +3111,10 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out, d, states);
   } else if (window) {
     rc = window_launch(ctx, w1, out, p->tap_w, halo / 64, halo % 64, planes, 0, u, p->sigma_y2, states, st, masks);
+    if (rc) return rc;
+  } else if (frames) {
+    rc = frames_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
+                       p->stride, 0, u, p->sigma_y2, states, st);
     if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
@@ -3051,7 +3339,7 @@ static int set_kernel_attributes() {
                                  (const void*)k_dct_sym<false, 1, 2>, (const void*)k_dct_sym<true, 1, 2>,
                                  (const void*)k_woodbury_inner,       (const void*)k_dct_rect<3>};
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-  for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up})
+  for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up, (const void*)k_conv_dec_frames, (const void*)k_conv_up_frames})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
   for (const void* fn : {(const void*)k_conv_window, (const void*)k_conv_window_masked})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
@@ -3626,6 +3914,32 @@ int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int ad
   return 0;
 }
 
+int fh_conv_frames(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx, const double* w,
+                   const int32_t* frame_off, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint,
+                   void* stream) {
+  if (!ctx || !in || !out || !dy || !dx || !w || !frame_off || in == out) return FH_EINVAL;
+  frames_choice c;
+  int rc = frames_plan(ctx->S, nframes, max_frame_taps, halo, planes, stride, adjoint, &c);  // every argument, before the copy below
+  if (rc) return rc;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  int ntaps = -1;  // the total tap count is the last offset: one read of all K + 1
+  rc = frames_prepare(ctx, frame_off, nframes, &ntaps, max_frame_taps, (hipStream_t)stream);
+  if (rc) return rc;
+  return frames_launch(ctx, in, out, dy, dx, w, frame_off, ntaps, nframes, max_frame_taps, halo, planes, stride, adjoint, nullptr,
+                       0.0, nullptr, (hipStream_t)stream);
+}
+
+int fh_conv_frames_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint, int32_t out[6]) {
+  if (out == nullptr) return FH_EINVAL;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  frames_choice c;
+  const int rc = frames_plan(S, nframes, max_frame_taps, halo, planes, stride, adjoint, &c);
+  if (rc) return rc;
+  const int32_t v[6] = {c.fused, (int32_t)c.grid.x, (int32_t)c.grid.y, (int32_t)c.grid.z, 256, (int32_t)c.lds};
+  memcpy(out, v, sizeof(v));
+  return 0;
+}
+
 int fh_conv_window(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes, int adjoint,
                    void* stream) {
   if (!ctx || !in || !out || !win || in == out) return FH_EINVAL;
@@ -3677,6 +3991,11 @@ int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, v
                        (int64_t)3 * So * So, (const fh_cg_state*)nullptr);
     return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, ctx->cg_p);
   }
+  if (p->op == 12) {
+    int total = p->ntaps;
+    const int rcf = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, (hipStream_t)stream);
+    if (rcf) return rcf;
+  }
   return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
 }
 
@@ -3727,9 +4046,13 @@ static hipGraphExec_t cg_graph_for(fh_context* ctx, const fh_problem* p, const f
   if (ctx->graphs_disabled) return nullptr;
   if (getenv("FH_NO_GRAPH") != nullptr) return nullptr;  // A/B switch for profiling
   ++ctx->graph_clock;
+  // op 12: the chain route bakes host-sliced tap pointers and counts into the graph, so the route switch and the offsets that
+  // frames_prepare has just checked (ctx->frame_off) belong to the key; other ops never read the switch
+  const int frames_route = p->op == 12 ? (int)frames_fused_on() : 0;
   fh_graph_entry* slot = &ctx->graphs[0];
   for (auto& g : ctx->graphs) {
     if (g.exec != nullptr && g.n == n && memcmp(&g.key, p, sizeof(fh_problem)) == 0 &&
+        (p->op != 12 || (g.frames_fused == frames_route && memcmp(g.frame_off, ctx->frame_off, sizeof(g.frame_off)) == 0)) &&
         memcmp(&g.bkey, &per, sizeof(fh_batch)) == 0) {
       g.stamp = ctx->graph_clock;
       return g.exec;
@@ -3770,6 +4093,8 @@ static hipGraphExec_t cg_graph_for(fh_context* ctx, const fh_problem* p, const f
   memcpy(&slot->key, p, sizeof(fh_problem));
   memcpy(&slot->bkey, &per, sizeof(fh_batch));
   slot->n = n;
+  slot->frames_fused = frames_route;
+  memcpy(slot->frame_off, ctx->frame_off, sizeof(slot->frame_off));
   slot->exec = exec;
   slot->graph = graph;
   slot->stamp = ctx->graph_clock;
@@ -3787,7 +4112,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (problem_check(p, S) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const int So = S / (decimating_op(p) ? p->stride : 1);
-  const int64_t n = (int64_t)(p->op == 3 ? 1 : p->planes) * So * So;  // measurement dimension per image (colorization: one plane)
+  const int64_t n = (int64_t)meas_planes(p) * So * So;  // measurement dimension per image (colorization: one plane, op 12: 3 K)
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;    // per image: [2]
@@ -3798,6 +4123,12 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
     if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
   int rc = colorize_prepare(ctx, p, per, st);
   if (rc) return rc;
+  if (p->op == 12) {  // the frame offsets, read and checked once per solve (the chain route launches from the host copy)
+    if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
+    int total = p->ntaps;
+    rc = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, st);
+    if (rc) return rc;
+  }
   if (masked_op(p)) {
     // masked blur: the system is solved for M b - the one masking of a solve; the iteration then needs no input-side mask
     // (amm_launch).  M b goes to cg_x for the first apply and, once that has released the work vectors, to w0 for k_cg_init

@@ -448,6 +448,198 @@ class CustomSROperator(CustomBlurOperator):
         return _SR_FOLD_CACHE[key]
 
 
+def shifted_psf(psf, dy, dx):
+    """The PSF of a frame displaced by (dy, dx) high-resolution pixels: the frame samples the blurred scene at
+    (s i + dy, s j + dx), and (B x)[i + dy] = sum_d k[d] x[i + dy - d] = sum_d' k[d' + dy] x[i - d'] - the PSF translated by
+    (-dy, -dx): a POSITIVE dy moves the entries UP (towards smaller row indices), a positive dx to the LEFT.  The integer part
+    moves entries exactly; the fractional part f in [0, 1) samples between two pixels, (1 - f) k[. + n] + f k[. + n + 1], the
+    2 x 2 bilinear kernel in two dimensions.  float64; the result is zero padded to odd sides with the centre kept at
+    size // 2, and the sum of the entries is preserved."""
+    k = np.asarray(psf, dtype=np.float64)
+    if k.ndim != 2 or k.size == 0:
+        raise ValueError(f"shifted_psf: the PSF must be a 2-D array, got shape {tuple(k.shape)}")
+    dy, dx = float(dy), float(dx)
+    if not (np.isfinite(dy) and np.isfinite(dx)):
+        raise ValueError(f"shifted_psf: the shift must be finite, got ({dy}, {dx})")
+
+    def axis(a, shift, ax):
+        """translate by -shift along `ax`; `a` has its centre at size // 2, so has the result"""
+        n = int(np.floor(shift))
+        f = shift - n
+        size, c = a.shape[ax], a.shape[ax] // 2
+        lo, hi = -c - n - (1 if f > 0 else 0), size - 1 - c - n  # offsets the entries land on
+        H = max(abs(lo), abs(hi), 0)
+        shape = list(a.shape)
+        shape[ax] = 2 * H + 1
+        out = np.zeros(shape)
+        sl = [slice(None)] * a.ndim
+        start = H - c - n  # index of the entry that had index 0
+        sl[ax] = slice(start, start + size)
+        if f > 0:
+            out[tuple(sl)] = (1.0 - f) * a
+            sl[ax] = slice(start - 1, start - 1 + size)
+            out[tuple(sl)] += f * a
+        else:
+            out[tuple(sl)] = a
+        return out
+
+    return axis(axis(k, dy, 0), dx, 1)
+
+
+class FrameTaps:
+    """The tap lists of a burst's K frames (`Taps` each) concatenated in frame order for fh_conv_frames / fh_problem.op = 12:
+    dy, dx, w [n], `off` int32 [K + 1] frame offsets (on the device), `max_taps` the longest frame, (hy, hx) the extents over
+    all frames and `halo` their 2-D code."""
+
+    def __init__(self, frames, device):
+        self.nframes = len(frames)
+        counts = [t.n for t in frames]
+        self.n, self.max_taps = int(sum(counts)), int(max(counts))
+        self.hy, self.hx = max(t.hy for t in frames), max(t.hx for t in frames)
+        self.halo = 1000 + 64 * self.hy + self.hx
+        self.dy = torch.cat([t.dy for t in frames]).contiguous()
+        self.dx = torch.cat([t.dx for t in frames]).contiguous()
+        self.w = torch.cat([t.w for t in frames]).contiguous()
+        self.off = torch.from_numpy(np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)).to(device)
+
+
+def parse_frame_shifts(shifts):
+    """`frame_shifts` as a list of (dy, dx) floats: a sequence of pairs, or the command line's "dy,dx;dy,dx;..." string"""
+    if isinstance(shifts, str):
+        try:
+            shifts = [tuple(float(v) for v in pair.split(",")) for pair in shifts.split(";") if pair.strip()]
+        except ValueError:
+            raise ValueError(f"burst_sr: frame_shifts is 'dy,dx;dy,dx;...' with numbers, got {shifts!r}") from None
+    out = [tuple(float(v) for v in np.asarray(p, dtype=np.float64).ravel()) for p in shifts]
+    if not out or any(len(p) != 2 or not np.isfinite(p).all() for p in out):
+        raise ValueError(f"burst_sr: frame_shifts is a non-empty list of finite (dy, dx) pairs, got {shifts!r}")
+    return out
+
+
+@register_operator(name="burst_sr")
+class BurstSROperator(LinearOperator):
+    """Multi-frame super-resolution: K low-resolution frames of one scene, each with its own PSF,
+        y_k = (B_k x)[..., ::s, ::s] + sigma_s n_k,   k = 0 .. K - 1,
+    B_k the circular blur of `custom_blur` (centre at index size // 2, rounded to float32, used as given), s = `scale_factor`
+    in {2, 3, 4}, a divisor of the image side that leaves at least 8 x 8 measurements, and 1 <= K <= s^2.  A frame's displacement
+    is part of its PSF: `frame_shifts` = K pairs (dy, dx) in high-resolution pixels translates the PSFs through `shifted_psf`
+    (frame k samples the blurred scene at (s i + dy_k, s j + dx_k)).
+      kernels       K 2-D arrays (or a [K, kh, kw] array)
+      kernel_path   a .npy with a [K, kh, kw] array, or with one 2-D PSF (then every shift applies to it)
+      frame_shifts  None, K pairs, or the string "dy,dx;dy,dx;..."; one PSF is repeated for every shift, K PSFs take one each
+    One sigma_s covers all frames.  The measurement is frame-major: [1, 3 K, So, So] with channel 3 k + c.  `forward` and
+    `transpose` are one A (fh_conv_frames); the solver's system is fh_problem.op = 12.  Every frame's PSF has at most
+    `Taps.MAX_TAPS` non-zeros and reaches at most 32 from its centre."""
+
+    def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernels=None, kernel_path=None, frame_shifts=None, **kwargs):
+        s = scale_factor
+        ok = isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, bool) and float(s) == int(s)
+        if not ok or int(s) not in (2, 3, 4):
+            raise ValueError(f"burst_sr: scale_factor must be 2, 3 or 4, got {scale_factor!r}")
+        s = int(s)
+        S = int(in_shape[-1])
+        if S % s != 0:
+            raise ValueError(f"burst_sr: scale_factor {s} does not divide the image side {S}")
+        if S // s < 8:
+            raise ValueError(f"burst_sr: scale_factor {s} leaves a {S // s} x {S // s} measurement of a {S} x {S} image; at "
+                             "least 8 x 8 is required")
+        if (kernel_path is None or kernel_path == "") == (kernels is None):
+            raise ValueError("burst_sr needs exactly one of kernels (K 2-D arrays) and kernel_path (a .npy file with a "
+                             "[K, kh, kw] array, or one 2-D PSF beside frame_shifts)")
+        if kernels is None:
+            arr = np.load(kernel_path)
+            if arr.ndim not in (2, 3):
+                raise ValueError(f"burst_sr: {kernel_path} must hold a [K, kh, kw] array or one 2-D PSF, got shape {tuple(arr.shape)}")
+            psfs = [arr] if arr.ndim == 2 else list(arr)
+        else:
+            psfs = [kernels] if (isinstance(kernels, np.ndarray) and kernels.ndim == 2) else list(kernels)
+        psfs = [np.asarray(k, dtype=np.float64) for k in psfs]
+        if not psfs or any(k.ndim != 2 or k.size == 0 for k in psfs):
+            raise ValueError("burst_sr: every frame's PSF must be a non-empty 2-D array")
+        if frame_shifts is not None and not (isinstance(frame_shifts, str) and frame_shifts == ""):
+            shifts = parse_frame_shifts(frame_shifts)
+            if len(psfs) == 1:
+                psfs = psfs * len(shifts)
+            if len(shifts) != len(psfs):
+                raise ValueError(f"burst_sr: {len(shifts)} frame_shifts for {len(psfs)} PSFs; give one shift per frame (or one PSF "
+                                 "for all shifts)")
+            psfs = [shifted_psf(k, dy, dx) for k, (dy, dx) in zip(psfs, shifts)]
+        K = len(psfs)
+        if not 1 <= K <= s * s:
+            raise ValueError(f"burst_sr: {K} frames at scale_factor {s}; the number of frames K is 1 .. s^2 = {s * s} (the "
+                             "measurement is never longer than the image)")
+        self.device = torch.device(device)
+        self.frames, self.kernels = [], []
+        for i, k in enumerate(psfs):
+            with np.errstate(over="ignore"):
+                k = np.asarray(k, dtype=np.float32)
+            if not np.isfinite(k).all():
+                raise ValueError(f"burst_sr: the PSF of frame {i} has a non-finite entry (also after rounding to float32)")
+            if not k.any():
+                raise ValueError(f"burst_sr: the PSF of frame {i} is all zero")
+            ys, xs = np.nonzero(k)
+            hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
+            if max(hy, hx) > 32:
+                raise ValueError(f"burst_sr: the PSF of frame {i} reaches ({hy}, {hx}) samples from its centre at index size // 2 "
+                                 "(its shift included); the kernels stage at most 32")
+            if ys.size > Taps.MAX_TAPS:
+                raise ValueError(f"burst_sr: the PSF of frame {i} has {ys.size} non-zeros, a tap list holds {Taps.MAX_TAPS}")
+            self.kernels.append(k)
+            self.frames.append(Taps(k, self.device))
+        self.frame_taps = FrameTaps(self.frames, self.device)
+        import ctypes
+        plan, out = _lib.load().fh_conv_frames_plan, (ctypes.c_int32 * 6)()
+        ft = self.frame_taps
+        for adjoint in (0, 1):
+            rc = plan(S, K, ft.max_taps, ft.halo, 3, s, adjoint, out)
+            if rc != 0:
+                raise ValueError(f"burst_sr: no kernel runs these tap lists (at most {ft.max_taps} taps per frame reaching "
+                                 f"({ft.hy}, {ft.hx})) at stride {s} on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
+        self.nframes = K
+        self.scale_factor = s
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
+        self.out_shape = (1, 3 * K, S // s, S // s)
+
+    def _conv(self, x, stride=None, adjoint=False):
+        """all frames' blur + decimation of an NCHW tensor [N,3,S,S] -> [N,3K,So,So] (frame-major), or the adjoint back;
+        float64.  (`stride` is the operator's own factor whatever the caller passes.)"""
+        S, s, K = self.in_shape[-1], self.scale_factor, self.nframes
+        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
+        N = x64.shape[0]
+        if adjoint:
+            assert tuple(x64.shape[1:]) == (3 * K, S // s, S // s), f"burst_sr: expected [N,{3 * K},{S // s},{S // s}], got {tuple(x64.shape)}"
+            out = torch.empty(N, 3, S, S, dtype=F64, device=self.device)
+        else:
+            assert tuple(x64.shape[1:]) == (3, S, S), f"burst_sr: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
+            out = torch.empty(N, 3 * K, S // s, S // s, dtype=F64, device=self.device)
+        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)  # (fh_conv_frames checks the planes it holds)
+        return ctx.blur_frames(x64, out, self.frame_taps, 3 * N, s, adjoint)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # ONE noise draw at the shape of the whole burst
+        y = self._noise(self._conv(data).to(data.dtype), noiseless)
+        self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.out_shape[-3:])
+        return self._conv(y, adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`, for DPS"""
+        return self._conv(v, adjoint=True).to(v.dtype)
+
+    def folded_bases(self):
+        return None
+
+    def folded_sr_bases(self):
+        return None  # (a rank-1 fold of the frames into rectangular bases is not built)
+
+
 def poisson_gaussian_sigma(y, gain, read_sigma):
     """Plug-in noise map of a Poisson-Gaussian sensor, sigma = 2 sqrt(gain clip((y + 1) / 2, 0, 1) + read_sigma^2): `y` in the
     [-1, 1] units of the measurements (array or tensor), `gain` and `read_sigma` in intensity units of [0, 1]; the factor 2 maps

@@ -209,6 +209,29 @@ int fh_conv_circ(fh_context* ctx, const double* in, double* out, const int32_t* 
  * 1 k_conv1d<1>, 2 k_conv_tile8, 3 k_conv_tile, 4 k_conv_dec, 5 k_conv_up, 6 k_conv_direct. */
 int fh_conv_circ_plan(int S, int ntaps, int halo, int planes, int stride, int adjoint, int32_t out[6]);
 
+/* Multi-frame super-resolution operator pair (fh_problem.op = 12): nframes = K frames of one scene, frame k the decimating
+ * convolution of fh_conv_circ at `stride` = s with its own tap list.  dy / dx / w hold the lists of all frames concatenated in
+ * frame order, frame_off is a DEVICE int32 [K + 1] of offsets into them (frame_off[0] = 0, frame_off[K] = the total, every frame
+ * 1 .. max_frame_taps long), halo the code 1000 + 64 hy + hx with the extents taken over ALL frames, planes = 3 * nimg.
+ *   adjoint = 0:  in [planes][S][S] -> out [nimg][K][3][So][So], So = S / s:   out_k = fh_conv_circ(in; frame k's list)
+ *   adjoint = 1:  in [nimg][K][3][So][So] -> out [planes][S][S]:               out = sum_k fh_conv_circ^T(in_k; frame k's list)
+ * Every frame's sum is one fma chain from 0 in list order; the adjoint adds the frames in index order, one rounding each: the
+ * result does not depend on the route.  Routes (frames_plan, csrc/fh_kernels.hip; fh_conv_frames_plan reports the decision
+ * without a context or a device, out = {route: 0 chain / 1 fused, grid x, grid y, grid z, block size, dynamic LDS bytes}, zeros
+ * on an error; on the chain the fields describe one of its launches: 3 planes, the longest frame):
+ *   fused: ONE launch of k_conv_dec_frames (So % 16 == 0) / k_conv_up_frames (S % 16 s == 0) where its LDS fits 100 KiB - the
+ *          full-resolution tile is staged once for all frames / written once;
+ *   chain: fh_conv_circ's launch per frame and image.  FH_FRAMES_FUSED=0 forces it (A/B switch).
+ * The call reads frame_off back (one stream synchronisation) and checks it.  FH_EINVAL before any launch: a null pointer,
+ * in == out, S odd or outside 2 .. 256, s outside 2 .. 4 or not a divisor of S, K < 1 or K > s^2, max_frame_taps outside
+ * 1 .. 1024, halo not a 2-D code with extents <= 32, planes < 3 or not a multiple of 3, adjoint outside 0 / 1, offsets that are
+ * not increasing from 0 or hold a frame longer than max_frame_taps; FH_ESIZE: planes beyond the context's (or 65535), or extents
+ * that fit no kernel's LDS. */
+int fh_conv_frames(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx, const double* w,
+                   const int32_t* frame_off, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint,
+                   void* stream);
+int fh_conv_frames_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint, int32_t out[6]);
+
 /* Circular 2-D convolution with a DENSE window win[2 hy + 1][2 hx + 1] (row-major, centre at (hy, hx), 0 <= hy, hx <= 32; zeros
  * inside the window are allowed) over in[planes][S][S] at stride 1 - fh_conv_circ's definition with dy = a, dx = b and no
  * limit on the number of non-zeros (a measured PSF, a defocus disk, a rotated Gaussian):
@@ -267,6 +290,14 @@ typedef struct fh_problem {
    * the weights of plane p at mask + (p % 3) n_plane, n_plane = S S (8 / 9) or So So (10 / 11).  mask == NULL (ops 8 .. 11, unlike
    * op 7) or a null per->mask[i]: FH_EINVAL before any launch.  All-ones weights give the bits of ops 1 / 4 / 2 / 7, 0/1 weights with
    * sigma_y2 = s^2 and b = M b0 those of ops 5 / 6.  The first such solve of a context allocates one more CG vector (W p).
+   * 12 multi-frame super-resolution on tap lists: K frames y_k = (B_k x)[::s, ::s] + n_k of one scene, A = [A_0; ..; A_{K-1}] the
+   * operator pair of fh_conv_frames.  stride = s in 2 .. 4, a divisor of S; tap_dy / tap_dx / tap_w the tap lists of all frames
+   * concatenated in frame order and ntaps their total; ntaps2 = K, 1 <= K <= s^2; tap2_dy a DEVICE int32 [K + 1] of frame offsets
+   * into the lists (tap2_dy[0] = 0, tap2_dy[K] = ntaps); halo2 the largest tap count of one frame, 1 .. 1024 (K <= ntaps <=
+   * K halo2); halo = 1000 + 64 hy + hx with the extents over ALL frames.  tap2_dx, tap2_w, the four fold_* and mask (per->mask[i])
+   * null, fold_sym = 0; use_dct 0 or 1.  The measurement - u, b, x - is [K][3][So][So] per image, n = 3 K So^2 <= 3 S^2.  A solve
+   * (and fh_amm) reads the offsets back and checks them once, before its launches.  Anything else: FH_EINVAL before any launch.
+   * No p.Ap partials come out of the operator: the CG runs its dot kernel, as for op 2.  K = 1 gives the bits of op 2.
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
