@@ -57,7 +57,16 @@ __global__ __launch_bounds__(256) void k_gemm_f64(const double* __restrict__ A, 
                                                   const fh_cg_state* __restrict__ states, int rows_per_plane,
                                                   const double* __restrict__ add, double add_scale) {
   constexpr int BM = 32 * TM, BN = 32 * TN, BK = 32, LD = BK + 2;
-  IMG_GUARD(states, ((int)blockIdx.z + (int)(blockIdx.y * BM) / rows_per_plane) / PPI);
+  if (states != nullptr) {
+    // Pass 1 runs over the rows of all planes at once, so where the rows of an image (PPI * S) are no multiple of BM a tile
+    // holds rows of several images: it is skipped only when every one of them has met its stopping rule (uniform).
+    const int row_hi = (int)(blockIdx.y * BM) + BM - 1 < M ? (int)(blockIdx.y * BM) + BM - 1 : M - 1;
+    int img = ((int)blockIdx.z + (int)(blockIdx.y * BM) / rows_per_plane) / PPI;
+    const int img_hi = ((int)blockIdx.z + row_hi / rows_per_plane) / PPI;
+    bool live = false;
+    for (; img <= img_hi; ++img) live = live || states[img].done == 0;
+    if (!live) return;
+  }
   __shared__ __align__(16) double As[2][BM][LD];
   __shared__ __align__(16) double Bs[2][BN][LD];
   A += sA * blockIdx.z;
@@ -2481,8 +2490,12 @@ __device__ __forceinline__ void conv1d_body(const double* __restrict__ in, doubl
   __syncthreads();
   for (int t = tid; t < ntaps; t += 256) e[(adjoint ? toff[t] : -toff[t]) + h] = tw[t];
   // stage: tile[a][c] = in at (along = a0 - h + a, across = c0 + c), circular.  All loads of a batch of 8 elements per
-  // thread are issued before the first LDS store (the staging is latency-bound otherwise); the wrap is a compare + add.
+  // thread are issued before the first LDS store (the staging is latency-bound otherwise); the wrap is a compare + add
+  // wherever one step of S brings every staged index a0 - h .. a0 + 31 + h into range (uniform over the workgroup; every
+  // S >= 64 with h <= 32), and a remainder where it does not: an image narrower than the tile, a list longer than the
+  // image.
   const int total = span * k1dAcross;
+  const bool wrap1 = a0 - h >= -S && a0 + k1dAlong - 1 + h < 2 * S;
   for (int base = 0; base < total; base += 256 * 8) {
     double v[8];
     int dst[8];
@@ -2493,6 +2506,7 @@ __device__ __forceinline__ void conv1d_body(const double* __restrict__ in, doubl
       if (AXIS == 0) a = idx / k1dAcross, c = idx % k1dAcross;  // consecutive lanes: consecutive x = across (coalesced)
       else c = idx / span, a = idx % span;                       // consecutive lanes: consecutive x = along (coalesced)
       int ga = a0 - h + a;
+      if (!wrap1) ga %= S;
       ga += ga < 0 ? S : 0;
       ga -= ga >= S ? S : 0;
       const int gc = c0 + c;

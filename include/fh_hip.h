@@ -199,6 +199,8 @@ int fh_read_scalars(fh_context* ctx, const double* scal, double* out_host, int k
  * -(h+101) (row kernel, all dy = 0), 2-D lists 1000 + 64 * max|dy| + max|dx|, so that only the needed halo is staged
  * (the shipped motion PSF spans 58 x 16: a third of the square halo).
  * Equals ifft2(FB * fft2(x)).real / ifft2(conj(FB) * fft2(x)).real of the reference.
+ * S is any even side the context admits and the extents may exceed it (a PSF wider than the image): every kernel reduces
+ * its staged indices mod S, so the taps wrap as often as the definition above says.
  * Which of the seven kernels runs, with what grid and LDS, is decided in one place, conv_plan (csrc/fh_kernels.hip);
  * fh_conv_circ_plan below reports that decision.  FH_EINVAL: a halo code outside the above, stride < 1 or not a divisor
  * of S, ntaps > 1024; FH_ESIZE: the halo and tap list fit no kernel's LDS. */

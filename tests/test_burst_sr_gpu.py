@@ -30,7 +30,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA = os.path.join(ROOT, "free-hunch_amd", "data")
 SIGMA_S = 0.05
 FUSED = [(64, 2), (64, 4), (96, 3)]
-CHAIN = [(80, 4)]  # So = 20: neither frame kernel tiles the image
+# So = 20: neither frame kernel tiles the image; (100, 4) and (60, 3): sides that are no multiple of 16, So = 25 (odd) and 20
+CHAIN = [(80, 4), (100, 4), (60, 3)]
 FOUR = [(0, 0), (0, 2), (2, 0), (2, 2)]  # K = 4 integer shifts at s = 4
 
 

@@ -87,6 +87,48 @@ def test_gpu_test_shapes_reach_the_kernels_they_name():
         assert tuple(got) == want, ((S, stride, kh, kw, density), got, want)
 
 
+# the cases test_conv_circ_matches_a_direct_sum adds at sides that are no multiple of 16: (forward, adjoint) kernel
+RAGGED = {
+    (100, 1, 9, 5, 0.5): ("k_conv_tile8", "k_conv_tile8"), (250, 1, 31, 7, 0.3): ("k_conv_tile8", "k_conv_tile8"),
+    (100, 1, 61, 61, 0.1): ("k_conv_tile", "k_conv_tile"), (6, 1, 5, 5, 1.0): ("k_conv_tile8", "k_conv_tile8"),
+    (20, 1, 61, 17, 0.2): ("k_conv_tile8", "k_conv_tile8"), (100, 1, 25, 1, 1.0): ("k_conv1d<0>", "k_conv1d<0>"),
+    (250, 1, 1, 61, 0.5): ("k_conv1d<1>", "k_conv1d<1>"), (100, 2, 7, 7, 1.0): ("k_conv_direct", "k_conv_tile"),
+    (100, 4, 25, 25, 1.0): ("k_conv_direct", "k_conv_tile"), (40, 4, 25, 25, 1.0): ("k_conv_direct", "k_conv_tile"),
+    (60, 3, 11, 9, 1.0): ("k_conv_direct", "k_conv_tile"), (20, 1, 61, 1, 1.0): ("k_conv1d<0>", "k_conv1d<0>"),
+    (6, 1, 1, 5, 1.0): ("k_conv1d<1>", "k_conv1d<1>"),
+}
+
+
+def test_ragged_shapes_reach_the_kernels_they_name():
+    """The same for the cases at sides that are no multiple of 16, with the grid each launch gets: whole tiles plus one
+    partial tile per direction.  k_conv_dec needs So % 16 == 0 and k_conv_up S % (16 s) == 0, hence S % 16 == 0: no ragged
+    side reaches them, and every decimating case here is on k_conv_direct / k_conv_tile with zero insertion."""
+    import numpy as np
+    lib, names = _lib(), _table()["kernels"]
+    from free_hunch_amd.measurements import _TapList
+    import torch
+    tile = {"k_conv1d<0>": (64, 32), "k_conv1d<1>": (32, 64), "k_conv_tile8": (32, 64), "k_conv_tile": (32, 16)}  # (x, y) outputs
+    reached = set()
+    for (S, stride, kh, kw, density), want in RAGGED.items():
+        assert S % 16 != 0
+        halo = _TapList(np.ones((kh, kw)), torch.device("cpu")).halo
+        got = []
+        for adjoint in (0, 1):
+            rc, out = _plan(lib, S, max(2, int(kh * kw * density)), halo, 3, stride, adjoint)
+            assert rc == 0, (S, stride, kh, kw, adjoint, rc)
+            name = names[out[0]]
+            got.append(name)
+            if name == "k_conv_direct":
+                So = S // stride
+                assert out[1:5] == [-(-3 * So * So // 256), 1, 1, 256] and out[5] == 0
+            else:
+                tx, ty = tile[name]
+                assert out[1:5] == [-(-S // tx), -(-S // ty), 3, 256] and 0 < out[5] <= 64 * 1024, (S, stride, kh, kw, out)
+        assert tuple(got) == want, ((S, stride, kh, kw, density), got, want)
+        reached.update(got)
+    assert reached == {"k_conv1d<0>", "k_conv1d<1>", "k_conv_tile8", "k_conv_tile", "k_conv_direct"}
+
+
 def test_plan_query_rejects_what_no_context_or_call_accepts():
     lib = _lib()
     for args in ((0, 9, 4, 3, 1, 0), (63, 9, 4, 3, 1, 0), (258, 9, 4, 3, 1, 0), (64, 0, 4, 3, 1, 0), (64, 9, 4, 0, 1, 0),

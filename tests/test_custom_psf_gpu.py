@@ -84,6 +84,11 @@ def _run_window(ctx, xd, wd, hy, hx, adjoint):
     (48, 9, 33, 0.0, 3),    # image smaller than the 64-row tile; a last tap block of one tap
     (64, 1, 1, 0.0, 3),     # no halo at all
     (256, 61, 61, 0.0, 6),  # 8 x 4 tiles, two images' planes
+    # sides that are no multiple of 16 (the table of tests/test_ragged_sizes_gpu.py)
+    (100, 61, 61, 0.0, 3),  # S % 8 = 4: the last tile column has 4 live outputs of a thread's 8, the last tile row 36 of 64
+    (250, 9, 33, 0.0, 3),   # S = 2 mod 4, 250 = 7 * 32 + 26 = 3 * 64 + 58
+    (20, 65, 65, 0.3, 3),   # a window larger than the image: every staged row and column wraps more than once
+    (6, 1, 1, 0.0, 3),      # an image smaller than a thread's 8 outputs
 ])
 def test_conv_window_matches_the_direct_sums(dev, S, kh, kw, zero, planes):
     """fh_conv_window forward and adjoint against the defining circular sums in NumPy float64, at the bounds

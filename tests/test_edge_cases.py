@@ -231,6 +231,21 @@ def _conv_circ_case(S, stride, kh, kw, density):
     (64, 1, 25, 1, 1.0),    # column list: k_conv1d<0>, whole tiles
     (96, 1, 1, 61, 0.5),    # row list with gaps: k_conv1d<1>, partial tiles both ways
     (64, 2, 9, 1, 1.0),     # 1-D code on the strided fallbacks: k_conv_direct, and k_conv_tile with zero insertion
+    # sides that are no multiple of 16 (the table of tests/test_ragged_sizes_gpu.py; the kernel each one reaches is held by
+    # test_ragged_shapes_reach_the_kernels_they_name in tests/test_conv_circ_plan.py)
+    (100, 1, 9, 5, 0.5),    # k_conv_tile8: the last 32-wide tile has 4 live columns, the last 64-tall tile 36 rows
+    (250, 1, 31, 7, 0.3),   # k_conv_tile8, S = 2 mod 4: 26 live columns, 58 live rows
+    (100, 1, 61, 61, 0.1),  # k_conv_tile: 100 = 3 * 32 + 4 = 6 * 16 + 4
+    (6, 1, 5, 5, 1.0),      # k_conv_tile8, an image smaller than every tile
+    (20, 1, 61, 17, 0.2),   # k_conv_tile8, a PSF taller than the image: the staged rows wrap three times
+    (100, 1, 25, 1, 1.0),   # k_conv1d<0>: 4 live outputs of the last thread's 8 along the filter, 36 of 64 lanes across
+    (250, 1, 1, 61, 0.5),   # k_conv1d<1>: 26 of 32 along, 58 of 64 across
+    (100, 2, 7, 7, 1.0),    # So = 50: no multiple of 16, so k_conv_direct / k_conv_tile with zero insertion
+    (100, 4, 25, 25, 1.0),  # So = 25, odd
+    (40, 4, 25, 25, 1.0),   # So = 10
+    (60, 3, 11, 9, 1.0),    # So = 20
+    (20, 1, 61, 1, 1.0),    # k_conv1d<0> with a list longer than the image (the staging's compare-and-add wrap does not reach)
+    (6, 1, 1, 5, 1.0),      # k_conv1d<1>, an image narrower than the 32 outputs of a tile: staged columns up to index 5 S
 ])
 def test_conv_circ_matches_a_direct_sum(S, stride, kh, kw, density):
     """fh_conv_circ over every kernel it dispatches to (k_conv1d<0>, k_conv1d<1>, k_conv_tile8, k_conv_tile, k_conv_dec,

@@ -204,7 +204,7 @@ def test_batched_cg_m0_symmetric_dct_equals_dense_passes(dev, tmp_path):
 
 
 # ---------------------------------------------------------------- batched covariance updates (one launch sequence for B images)
-@pytest.mark.parametrize("S", [64, 256])
+@pytest.mark.parametrize("S", [64, 100, 256])  # 100: d = 30000 = 39 * 768 + 48, no multiple of any kernel's row block
 def test_batched_covariance_updates_equal_per_image_bitwise(dev, S):
     """fh_cov_time_update_batched / fh_cov_space_update_batched (the update kernels with the image as a grid dimension and
     per-image pointer tables) against the per-object update_time_step / update_space_step on three images with different
