@@ -32,6 +32,9 @@ def dev():
 
 
 def _psf(kind):
+    """the PSF named `kind`; an array is a PSF of the caller's own (tests/test_ragged_ops_gpu.py: PSFs that fit a small side)"""
+    if isinstance(kind, np.ndarray):
+        return kind
     return disk_psf() if kind == "disk" else np.load(os.path.join(DATA, "kernels", SHIPPED[kind]))
 
 
