@@ -65,19 +65,23 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 # fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
 # (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
 # into rectangular DCT bases op = 7, see _problem; a weighted_blur on the dense-window kernel is op = 9, a weighted_sr on the
-# rectangular bases op = 11; burst_sr is op = 12, the multi-frame operator pair of fh_conv_frames)
+# rectangular bases op = 11; burst_sr is op = 12, the multi-frame operator pair of fh_conv_frames, and weighted_burst_sr is
+# op = 13, the same pair with a noise map on the burst)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
             "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10,
-            "burst_sr": 12}
+            "burst_sr": 12, "weighted_burst_sr": 13}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
 # operators whose PSF is the caller's: a lock-step batch must share it
 _SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr")
 # operators with a scale_factor: A = blur + decimation on the PSF's tap list
-_DECIMATING = ("super_resolution", "custom_sr", "weighted_sr", "burst_sr")
-# operators with a per-pixel noise map: the solver whitens with operator.weights = 1 / sigma_i and sigma_y2 = 1 (ops 8 .. 11)
-_WEIGHTED = ("weighted_blur", "weighted_sr")
+_DECIMATING = ("super_resolution", "custom_sr", "weighted_sr", "burst_sr", "weighted_burst_sr")
+# operators with a per-pixel noise map: the solver whitens with operator.weights = 1 / sigma_i and sigma_y2 = 1 (ops 8 .. 11, 13)
+_WEIGHTED = ("weighted_blur", "weighted_sr", "weighted_burst_sr")
+# operators on K frames with one PSF each: A is the operator pair of fh_conv_frames, the measurement [3 K, So, So] per image
+_BURST = ("burst_sr", "weighted_burst_sr")
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'. Also 'burst_sr'.")
+                 "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'. Also 'burst_sr' and "
+                 "'weighted_burst_sr'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -105,12 +109,16 @@ def _problem(operator, cov, sigma_y2):
         p.mask = mask.data_ptr()
         keep.append(mask)
         return p, keep
-    if operator.name == "burst_sr":  # op 12: the frames' tap lists concatenated, their offsets in tap2_dy (include/fh_hip.h)
+    if operator.name in _BURST:  # ops 12 / 13: the frames' tap lists concatenated, their offsets in tap2_dy (include/fh_hip.h)
         ft = operator.frame_taps
         p.ntaps, p.halo = ft.n, ft.halo
         p.tap_dy, p.tap_dx, p.tap_w = ft.dy.data_ptr(), ft.dx.data_ptr(), ft.w.data_ptr()
         p.ntaps2, p.halo2, p.tap2_dy = ft.nframes, ft.max_taps, ft.off.data_ptr()
         keep.extend([ft.dy, ft.dx, ft.w, ft.off])
+        if operator.name in _WEIGHTED:  # op 13: the weights [3 K, So, So], frame-major like the measurement; kept LAST in `keep`
+            w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
+            p.mask = w.data_ptr()
+            keep.append(w)
         return p, keep
     if operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
@@ -247,7 +255,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
         if name in _SHARED_PSF:
             assert torch.equal(op.taps.kernel, op0.taps.kernel), "lock-step images must share the PSF"
-        if name == "burst_sr":
+        if name in _BURST:
             assert op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in
                                                      zip(op.kernels, op0.kernels)), \
                 "lock-step images must share the PSF of every frame"
@@ -268,7 +276,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     def conv(v, adjoint):
         """op0's blur on the whole batch (planes = 3B)"""
         so = S if (adjoint or prob.stride == 1) else S // prob.stride
-        if name == "burst_sr":  # all frames of all images: [B,3,S,S] <-> [B,3K,So,So]
+        if name in _BURST:  # all frames of all images: [B,3,S,S] <-> [B,3K,So,So]
             out = torch.empty(B, 3 if adjoint else 3 * op0.nframes, so, so, dtype=F64, device=dev)
             return ctx.blur_frames(v, out, op0.frame_taps, planes, prob.stride, adjoint)
         out = torch.empty(B, 3, so, so, dtype=F64, device=dev)

@@ -62,6 +62,11 @@ SCHEMA = {
     # a [K, kh, kw] array of per-frame PSFs, or one 2-D PSF that --frame_shifts="dy,dx;dy,dx;..." (K pairs, high-resolution pixels,
     # fractions allowed) displaces per frame; with K PSFs the K shifts apply one each
     "frame_shifts": (str, ""),
+    # NEW: --operator_name=weighted_burst_sr, burst_sr (same --kernel_path, --scale_factor, --frame_shifts) with a noise level per
+    # pixel of every frame: one of --noise_map_path (a .npy [So,So] / [3,So,So] for every frame, or [K,3,So,So] / [3K,So,So] /
+    # [1,3K,So,So]), --frame_sigmas="a,b,c,..." (one level per frame, inf drops a frame) and the sensor pair --noise_gain /
+    # --noise_read_sigma; --mosaic=rggb | bggr | grbg | gbrg makes every frame a raw Bayer frame (one channel per site)
+    "frame_sigmas": (str, ""), "mosaic": (str, ""),
 }
 
 
@@ -97,14 +102,24 @@ def load_config(argv=None):
                              "mask use --operator_name=custom_blur)")
     if cfg["operator_name"] == "custom_sr" and not cfg["kernel_path"]:
         raise SystemExit("--operator_name=custom_sr needs --kernel_path=FILE.npy (the PSF, a 2-D array) beside --scale_factor")
-    if cfg["operator_name"] == "burst_sr" and not cfg["kernel_path"]:
-        raise SystemExit("--operator_name=burst_sr needs --kernel_path=FILE.npy (a [K, kh, kw] array of per-frame PSFs, or one 2-D "
+    if cfg["operator_name"] in ("burst_sr", "weighted_burst_sr") and not cfg["kernel_path"]:
+        raise SystemExit(f"--operator_name={cfg['operator_name']} needs --kernel_path=FILE.npy (a [K, kh, kw] array of per-frame PSFs, or one 2-D "
                          "PSF beside --frame_shifts) beside --scale_factor")
-    if cfg["frame_shifts"] and cfg["operator_name"] != "burst_sr":
-        raise SystemExit(f"--frame_shifts belongs to --operator_name=burst_sr; operator '{cfg['operator_name']}' does not read it")
+    if cfg["frame_shifts"] and cfg["operator_name"] not in ("burst_sr", "weighted_burst_sr"):
+        raise SystemExit(f"--frame_shifts belongs to --operator_name=burst_sr (and weighted_burst_sr); operator "
+                         f"'{cfg['operator_name']}' does not read it")
+    if (cfg["frame_sigmas"] or cfg["mosaic"]) and cfg["operator_name"] != "weighted_burst_sr":
+        raise SystemExit(f"--frame_sigmas and --mosaic belong to --operator_name=weighted_burst_sr; operator "
+                         f"'{cfg['operator_name']}' does not read them")
     weighted = cfg["operator_name"] in ("weighted_blur", "weighted_sr")
     sensor = cfg["noise_gain"] is not None or cfg["noise_read_sigma"] is not None
-    if weighted:
+    if cfg["operator_name"] == "weighted_burst_sr":
+        if sensor and (cfg["noise_gain"] is None or cfg["noise_read_sigma"] is None):
+            raise SystemExit("--noise_gain and --noise_read_sigma go together: the Poisson-Gaussian noise map needs both")
+        if bool(cfg["noise_map_path"]) + bool(cfg["frame_sigmas"]) + sensor != 1:
+            raise SystemExit("--operator_name=weighted_burst_sr needs a noise map: exactly one of --noise_map_path=FILE.npy, "
+                             "--frame_sigmas=\"a,b,c,...\" and --noise_gain=G --noise_read_sigma=R")
+    elif weighted:
         if not cfg["kernel_path"]:
             raise SystemExit(f"--operator_name={cfg['operator_name']} needs --kernel_path=FILE.npy (the PSF, a 2-D array)")
         if sensor and (cfg["noise_gain"] is None or cfg["noise_read_sigma"] is None):
@@ -114,13 +129,13 @@ def load_config(argv=None):
                              "--noise_gain=G --noise_read_sigma=R, not both")
     elif cfg["noise_map_path"] or sensor:
         raise SystemExit(f"--noise_map_path, --noise_gain and --noise_read_sigma belong to --operator_name=weighted_blur / "
-                         f"weighted_sr; operator '{cfg['operator_name']}' does not read them")
+                         f"weighted_sr / weighted_burst_sr; operator '{cfg['operator_name']}' does not read them")
     if cfg["operator_name"] != "masked_blur" and (cfg["mask_path"] or cfg["mask_border"] != 0):
         raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
     if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr", "weighted_blur",
-                                                           "weighted_sr", "burst_sr"):
+                                                           "weighted_sr", "burst_sr", "weighted_burst_sr"):
         raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr / weighted_blur / "
-                         f"weighted_sr / burst_sr; operator "
+                         f"weighted_sr / burst_sr / weighted_burst_sr; operator "
                          f"'{cfg['operator_name']}' does not read it")
     return SimpleNamespace(**cfg)

@@ -2139,6 +2139,10 @@ __global__ __launch_bounds__(256) void k_conv_up(const double* __restrict__ in, 
 //                       each - the bits of K k_conv_up launches chained through add (add_scale = 1).  One coalesced store.
 // Both read their frame's taps inside [0, ntaps) and at most cap_taps / cap of them whatever foff holds (the host has checked
 // foff before the launch, frames_prepare); the tile indices trust hy / hx like the single-frame kernels.  No atomics.
+// WEIGHTED (op 13, k_conv_dec_frames_w): the epilogue multiplies the frame's sum by the weight of its output, wt.D[image] at the
+// output's offset inside the image ([K][3][So][So], the measurement's own layout), rounds, and then adds: k_mask's expression,
+// fma(add_scale, add, w * t).  A compile-time flag, as MASKED in the convolution kernels: k_conv_dec_frames instantiates
+// `false` and never touches wt.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void frame_range(const int* __restrict__ foff, int k, int ntaps, int* t0, int* n) {
   int a = foff[k], b = foff[k + 1];
@@ -2147,12 +2151,13 @@ __device__ __forceinline__ void frame_range(const int* __restrict__ foff, int k,
   *t0 = a, *n = b - a;
 }
 
-__global__ __launch_bounds__(256) void k_conv_dec_frames(const double* __restrict__ in, double* __restrict__ out,
-                                                         const int* __restrict__ tdy, const int* __restrict__ tdx,
-                                                         const double* __restrict__ tw, const int* __restrict__ foff,
-                                                         int K, int ntaps, int cap_taps, int S, int s, int hy, int hx,
-                                                         const double* __restrict__ add, double add_scale,
-                                                         const fh_cg_state* __restrict__ states) {
+template <bool WEIGHTED>
+__device__ __forceinline__ void conv_dec_frames_body(const double* __restrict__ in, double* __restrict__ out,
+                                                     const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                     const double* __restrict__ tw, const int* __restrict__ foff,
+                                                     int K, int ntaps, int cap_taps, int S, int s, int hy, int hx,
+                                                     const double* __restrict__ add, double add_scale,
+                                                     const fh_cg_state* __restrict__ states, const fh_diag_tab& wt) {
   IMG_GUARD(states, blockIdx.z / 3);
   extern __shared__ __align__(16) double tile[];
   const int So = S / s;
@@ -2195,10 +2200,30 @@ __global__ __launch_bounds__(256) void k_conv_dec_frames(const double* __restric
     }
     if (oy < So && ox < So) {
       const int64_t o = ((int64_t)(img * K + k) * 3 + ch) * So * So + (int64_t)oy * So + ox;
+      if (WEIGHTED) acc = wt.D[img][(int64_t)(k * 3 + ch) * So * So + (int64_t)oy * So + ox] * acc;
       if (add != nullptr) acc = fma(add_scale, add[o], acc);
       out[o] = acc;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_conv_dec_frames(const double* __restrict__ in, double* __restrict__ out,
+                                                         const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                         const double* __restrict__ tw, const int* __restrict__ foff,
+                                                         int K, int ntaps, int cap_taps, int S, int s, int hy, int hx,
+                                                         const double* __restrict__ add, double add_scale,
+                                                         const fh_cg_state* __restrict__ states) {
+  conv_dec_frames_body<false>(in, out, tdy, tdx, tw, foff, K, ntaps, cap_taps, S, s, hy, hx, add, add_scale, states,
+                              fh_diag_tab{});
+}
+
+__global__ __launch_bounds__(256) void k_conv_dec_frames_w(const double* __restrict__ in, double* __restrict__ out,
+                                                           const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                           const double* __restrict__ tw, const int* __restrict__ foff,
+                                                           int K, int ntaps, int cap_taps, int S, int s, int hy, int hx,
+                                                           const double* __restrict__ add, double add_scale,
+                                                           const fh_cg_state* __restrict__ states, fh_diag_tab wt) {
+  conv_dec_frames_body<true>(in, out, tdy, tdx, tw, foff, K, ntaps, cap_taps, S, s, hy, hx, add, add_scale, states, wt);
 }
 
 __global__ __launch_bounds__(256) void k_conv_up_frames(const double* __restrict__ in, double* __restrict__ out,
@@ -2758,8 +2783,8 @@ static int frames_plan(int S, int nframes, int max_frame_taps, int halo, int pla
   return 0;
 }
 
-// FH_FRAMES_FUSED=0: the chain also where the fused kernels fit (A/B switch, like FH_CG_NO_DOT_FUSE).  Read at every op 12
-// call (and by no other op), so one process can time both routes; the CG graph cache keys on it for op 12
+// FH_FRAMES_FUSED=0: the chain also where the fused kernels fit (A/B switch, like FH_CG_NO_DOT_FUSE).  Read at every op 12 / 13
+// call (and by no other op), so one process can time both routes; the CG graph cache keys on it for ops 12 / 13
 // (fh_graph_entry.frames_fused).
 static bool frames_fused_on() {
   const char* v = getenv("FH_FRAMES_FUSED");
@@ -2784,21 +2809,38 @@ static int frames_prepare(fh_context* ctx, const int32_t* frame_off, int nframes
   return 0;
 }
 
+// the weights of ops 8 .. 11 and 13 as the per-image table of k_cg_init_w / k_cg_step2_w and of k_conv_dec_frames_w
+static fh_diag_tab weights_tab(const fh_batch& per) {
+  fh_diag_tab wt;
+  memset(&wt, 0, sizeof(wt));
+  for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i) wt.D[i] = per.mask[i];
+  return wt;
+}
+
 // in [planes][S][S] -> out [nimg][K][3][So][So] (+ add_scale * add in that layout), or with `adjoint` back (no add).
 // frames_prepare has run for these offsets.
+// masks (op 13, forward only): the weights, masks->mask[i] = [K][3][So][So] of image i, multiplied in as k_mask does,
+// out = add_scale * add + w .* conv(in): the fused kernel in its epilogue; the chain through conv_launch's masks / spare path,
+// one one-image table per (image, frame) whose entry is that frame's three planes, with the frame's own slice of `spare` (a
+// work vector of the caller's in the output's layout, not in / out / add) between the decimating pass and k_mask.
 static int frames_launch(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx,
                          const double* w, const int32_t* frame_off, int ntaps, int nframes, int max_frame_taps, int halo,
                          int planes, int stride, int adjoint, const double* add, double add_scale, const fh_cg_state* done,
-                         hipStream_t st) {
+                         hipStream_t st, const fh_batch* masks = nullptr, double* spare = nullptr) {
   const int S = ctx->S;
   frames_choice c;
   const int rc = frames_plan(S, nframes, max_frame_taps, halo, planes, stride, adjoint, &c);
   if (rc) return rc;
   if (planes > ctx->planes_max) return FH_ESIZE;
+  if (masks != nullptr && (adjoint || spare == nullptr || planes != 3 * masks->nimg || masks->nimg > FH_MAX_BATCH))
+    return FH_EINVAL;
   if (c.fused && frames_fused_on()) {
     if (adjoint)
       hipLaunchKernelGGL(k_conv_up_frames, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps, S, stride,
                          c.hy, c.hx, c.cap, done);
+    else if (masks != nullptr)
+      hipLaunchKernelGGL(k_conv_dec_frames_w, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps,
+                         max_frame_taps, S, stride, c.hy, c.hx, add, add_scale, done, weights_tab(*masks));
     else
       hipLaunchKernelGGL(k_conv_dec_frames, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps,
                          max_frame_taps, S, stride, c.hy, c.hx, add, add_scale, done);
@@ -2816,7 +2858,14 @@ static int frames_launch(fh_context* ctx, const double* in, double* out, const i
       if (adjoint)
         rc2 = conv_launch(ctx, in + f, out + i * hi, dy + t0, dx + t0, w + t0, n, halo, 3, stride, 1,
                           k > 0 ? out + i * hi : nullptr, 1.0, di, st);
-      else
+      else if (masks != nullptr) {
+        fh_batch one;  // k_mask of an nimg = 1 launch reads mask[0], in, out and add from their bases: all four at this frame
+        memset(&one, 0, sizeof(one));
+        one.nimg = 1;
+        one.mask[0] = masks->mask[i] + (int64_t)k * lo;
+        rc2 = conv_launch(ctx, in + i * hi, out + f, dy + t0, dx + t0, w + t0, n, halo, 3, stride, 0,
+                          add != nullptr ? add + f : nullptr, add_scale, di, st, &one, spare + f);
+      } else
         rc2 = conv_launch(ctx, in + i * hi, out + f, dy + t0, dx + t0, w + t0, n, halo, 3, stride, 0,
                           add != nullptr ? add + f : nullptr, add_scale, di, st);
       if (rc2) return rc2;
@@ -2869,13 +2918,14 @@ static int window_problem_check(const fh_problem* p) {
 // (the masks of a batched solve are per->mask[i]: masks_check)
 // S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 12) return FH_EINVAL;
-  if (p->op == 12) {  // multi-frame SR: stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
+  if (p->op < 0 || p->op > 13) return FH_EINVAL;
+  if (p->op == 12 || p->op == 13) {  // multi-frame SR: stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
+    // (op 13 brings the weights in mask: masks_check refuses a null one)
     const int s = p->stride, K = p->ntaps2;
     if (s < 2 || s > 4 || S % s != 0 || K < 1 || K > s * s) return FH_EINVAL;
     if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
     if (p->halo < 1000 || p->tap2_dy == nullptr || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
-    if (p->tap2_dx || p->tap2_w || p->mask || p->fold_sym != 0) return FH_EINVAL;
+    if (p->tap2_dx || p->tap2_w || (p->op == 12 && p->mask) || p->fold_sym != 0) return FH_EINVAL;
     if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
     return 0;
   }
@@ -2894,10 +2944,15 @@ static int problem_check(const fh_problem* p, int S) {
 static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
 // ops 8 .. 11 (per-pixel noise map): the mask field carries the weights w = 1 / sigma, [3][n][n] per image at the
 // measurement's side n (S for ops 8 / 9, S / stride for ops 10 / 11)
-static bool weighted_op(const fh_problem* p) { return p->op >= 8 && p->op <= 11; }
-static bool decimating_op(const fh_problem* p) { return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || p->op == 12; }
-// measurement planes per image: one for colorization, 3 K for the K frames of op 12, else 3
-static int meas_planes(const fh_problem* p) { return p->op == 3 ? 1 : (p->op == 12 ? p->ntaps2 : 1) * p->planes; }
+// op 13 (the noise map on the burst of op 12): [K][3][So][So] per image, the measurement's own frame-major layout
+static bool weighted_op(const fh_problem* p) { return (p->op >= 8 && p->op <= 11) || p->op == 13; }
+// ops 12 / 13 (multi-frame SR): ntaps2 counts frames, tap2_dy holds their offsets
+static bool frames_op(const fh_problem* p) { return p->op == 12 || p->op == 13; }
+static bool decimating_op(const fh_problem* p) {
+  return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || frames_op(p);
+}
+// measurement planes per image: one for colorization, 3 K for the K frames of ops 12 / 13, else 3
+static int meas_planes(const fh_problem* p) { return p->op == 3 ? 1 : (frames_op(p) ? p->ntaps2 : 1) * p->planes; }
 static int masks_check(const fh_problem* p, const fh_batch& per) {
   if (p->op == 7 || p->op == 12) {  // no mask on the low-resolution measurement
     for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
@@ -2959,6 +3014,9 @@ static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch
 // k_mask pass over the 3 So^2 measurements behind its decimating kernel.  W is not idempotent, so the input side cannot be
 // skipped: every caller hands in uin = W u - fh_amm from a k_mask pass, the CG from the direction update that writes p
 // (k_cg_init_w / k_cg_step2_w keep W p beside p).  u itself stays the add / dot operand: the partials are p . A_mm(p).
+// Op 13 is op 12 in the same way: the adjoint frame kernels read uin = W u, and the forward ones finish with the weights
+// (frames_launch: the WEIGHTED epilogue of the fused kernel, or k_mask per frame on the chain) - the same expression, so
+// the two routes agree bit for bit, all-ones weights with sigma_y^2 = s^2 give op 12 and K = 1 gives op 10.
 static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* u, double* out,
                       const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr,
                       const double* uin = nullptr) {
@@ -3043,7 +3101,7 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   }
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
-  const bool frames = p->op == 12;                // multi-frame SR: ntaps2 counts frames, tap2_dy holds their offsets
+  const bool frames = frames_op(p);               // multi-frame SR: ntaps2 counts frames, tap2_dy holds their offsets
   const bool sep = !frames && p->ntaps2 > 0;      // separable PSF: two 1-D passes (blur only, stride 1)
   if (sep && p->stride != 1) return FH_EINVAL;
   if (blur && p->use_dct && p->fold_fwd_w != nullptr) {
@@ -3128,7 +3186,7 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     if (rc) return rc;
   } else if (frames) {
     rc = frames_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
-                       p->stride, 0, u, p->sigma_y2, states, st);
+                       p->stride, 0, u, p->sigma_y2, states, st, masks, w0);  // (op 13: w0 is the spare, as below)
     if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
@@ -3353,7 +3411,8 @@ static int set_kernel_attributes() {
                                  (const void*)k_dct_sym<false, 1, 2>, (const void*)k_dct_sym<true, 1, 2>,
                                  (const void*)k_woodbury_inner,       (const void*)k_dct_rect<3>};
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
-  for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up, (const void*)k_conv_dec_frames, (const void*)k_conv_up_frames})
+  for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up, (const void*)k_conv_dec_frames,
+                         (const void*)k_conv_dec_frames_w, (const void*)k_conv_up_frames})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
   for (const void* fn : {(const void*)k_conv_window, (const void*)k_conv_window_masked})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
@@ -3996,29 +4055,21 @@ int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, v
   if (masks_check(p, per)) return FH_EINVAL;
   const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
   if (rc) return rc;
+  if (frames_op(p)) {  // (before the first launch of op 13 as well)
+    int total = p->ntaps;
+    const int rcf = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, (hipStream_t)stream);
+    if (rcf) return rcf;
+  }
   if (masked_op(p) || weighted_op(p)) {
     // the input-side mask / weights of A_mm (amm_launch): M u or W u into a CG vector, which is idle outside a solve
     if (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3) return FH_EINVAL;
     if (ctx->planes_max < 3) return FH_ESIZE;
     const int So = ctx->S / (decimating_op(p) ? p->stride : 1);
     hipLaunchKernelGGL(k_mask, dim3(512, 1, 1), dim3(256), 0, (hipStream_t)stream, per, u, (const double*)nullptr, 0.0, ctx->cg_p,
-                       (int64_t)3 * So * So, (const fh_cg_state*)nullptr);
+                       (int64_t)meas_planes(p) * So * So, (const fh_cg_state*)nullptr);
     return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, ctx->cg_p);
   }
-  if (p->op == 12) {
-    int total = p->ntaps;
-    const int rcf = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, (hipStream_t)stream);
-    if (rcf) return rcf;
-  }
   return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
-}
-
-// the weights of ops 8 .. 11 as the per-image table of k_cg_init_w / k_cg_step2_w
-static fh_diag_tab weights_tab(const fh_batch& per) {
-  fh_diag_tab wt;
-  memset(&wt, 0, sizeof(wt));
-  for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i) wt.D[i] = per.mask[i];
-  return wt;
 }
 
 // One chunk of CG iterations for all images of the batch, enqueued on `st` (eagerly, or while the stream is being
@@ -4060,13 +4111,14 @@ static hipGraphExec_t cg_graph_for(fh_context* ctx, const fh_problem* p, const f
   if (ctx->graphs_disabled) return nullptr;
   if (getenv("FH_NO_GRAPH") != nullptr) return nullptr;  // A/B switch for profiling
   ++ctx->graph_clock;
-  // op 12: the chain route bakes host-sliced tap pointers and counts into the graph, so the route switch and the offsets that
-  // frames_prepare has just checked (ctx->frame_off) belong to the key; other ops never read the switch
-  const int frames_route = p->op == 12 ? (int)frames_fused_on() : 0;
+  // ops 12 / 13: the chain route bakes host-sliced tap pointers and counts into the graph, so the route switch and the offsets
+  // that frames_prepare has just checked (ctx->frame_off) belong to the key; other ops never read the switch.  (The weights'
+  // pointers of op 13 are part of bkey, like those of ops 8 .. 11; their values are read by the kernels at every replay.)
+  const int frames_route = frames_op(p) ? (int)frames_fused_on() : 0;
   fh_graph_entry* slot = &ctx->graphs[0];
   for (auto& g : ctx->graphs) {
     if (g.exec != nullptr && g.n == n && memcmp(&g.key, p, sizeof(fh_problem)) == 0 &&
-        (p->op != 12 || (g.frames_fused == frames_route && memcmp(g.frame_off, ctx->frame_off, sizeof(g.frame_off)) == 0)) &&
+        (!frames_op(p) || (g.frames_fused == frames_route && memcmp(g.frame_off, ctx->frame_off, sizeof(g.frame_off)) == 0)) &&
         memcmp(&g.bkey, &per, sizeof(fh_batch)) == 0) {
       g.stamp = ctx->graph_clock;
       return g.exec;
@@ -4126,7 +4178,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   if (problem_check(p, S) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
   if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const int So = S / (decimating_op(p) ? p->stride : 1);
-  const int64_t n = (int64_t)meas_planes(p) * So * So;  // measurement dimension per image (colorization: one plane, op 12: 3 K)
+  const int64_t n = (int64_t)meas_planes(p) * So * So;  // per image (colorization: one plane, ops 12 / 13: 3 K)
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;    // per image: [2]
@@ -4137,7 +4189,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
     if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
   int rc = colorize_prepare(ctx, p, per, st);
   if (rc) return rc;
-  if (p->op == 12) {  // the frame offsets, read and checked once per solve (the chain route launches from the host copy)
+  if (frames_op(p)) {  // the frame offsets, read and checked once per solve (the chain route launches from the host copy)
     if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
     int total = p->ntaps;
     rc = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, st);

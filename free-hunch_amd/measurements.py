@@ -741,6 +741,112 @@ class WeightedSROperator(_NoiseMap, CustomSROperator):
         return self._conv(v * self.mask.to(v.dtype), stride=self.scale_factor, adjoint=True).to(v.dtype)
 
 
+BAYER_PATTERNS = ("rggb", "bggr", "grbg", "gbrg")
+
+
+def bayer_sites(n, pattern):
+    """Boolean [3, n, n] array of a Bayer mosaic (True = the site samples that channel; exactly one channel per site).  The
+    four letters of `pattern` are the 2 x 2 cell read row-major - (even row, even column), (even, odd), (odd, even),
+    (odd, odd) - with channels r = 0, g = 1, b = 2."""
+    if not isinstance(pattern, str) or pattern.lower() not in BAYER_PATTERNS:
+        raise ValueError(f"bayer_sites: the pattern is one of {', '.join(BAYER_PATTERNS)}, got {pattern!r}")
+    n = int(n)
+    sites = np.zeros((3, n, n), dtype=bool)
+    for i, letter in enumerate(pattern.lower()):
+        sites["rgb".index(letter), i // 2::2, i % 2::2] = True
+    return sites
+
+
+def parse_frame_sigmas(sigmas):
+    """`frame_sigmas` as a float64 array: a sequence of numbers, or the command line's "a,b,c" string ("inf" drops a frame)"""
+    if isinstance(sigmas, str):
+        try:
+            sigmas = [float(v) for v in sigmas.split(",") if v.strip()]
+        except ValueError:
+            raise ValueError(f"weighted_burst_sr: frame_sigmas is 'a,b,c,...' with numbers, got {sigmas!r}") from None
+    return np.asarray(sigmas, dtype=np.float64).ravel()
+
+
+@register_operator(name="weighted_burst_sr")
+class WeightedBurstSROperator(_NoiseMap, BurstSROperator):
+    """`burst_sr` (same PSF, shift and factor arguments, checks and kernels) with a per-pixel noise level on every frame,
+    y_k = (B_k x)[..., ::s, ::s] + n_k with n ~ N(0, diag(sigma^2)), sigma in (0, inf], inf = not measured - see `_NoiseMap`, here
+    at the burst's shape: `noise_map`, `weights` and `mask` are float64 [1, 3 K, So, So], frame-major like the measurement
+    (channel 3 k + c).  Exactly one noise source:
+      noise_map       array / tensor [So,So] or [3,So,So] (the same for every frame), [K,3,So,So], [3K,So,So] or [1,3K,So,So]
+      noise_map_path  a .npy of the same shapes
+      frame_sigmas    K numbers (or the string "a,b,c"), one level per frame; inf drops a frame
+    `mosaic` = "rggb" / "bggr" / "grbg" / "gbrg" (`bayer_sites`, the same pattern for every frame) sets the entries of the
+    channels a site does not sample to inf on top of that source: joint demosaicing and super-resolution from raw frames.
+    The solver's system is fh_problem.op = 13; the adjoint stays unweighted, `transpose` = `forward_adjoint` = A^T (mask * v)."""
+    _NOISE_FLOOR = 0.01
+
+    def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernels=None, kernel_path=None, frame_shifts=None,
+                 noise_map=None, noise_map_path=None, frame_sigmas=None, mosaic=None, **kwargs):
+        BurstSROperator.__init__(self, in_shape, sigma_s, device, scale_factor=scale_factor, kernels=kernels,
+                                 kernel_path=kernel_path, frame_shifts=frame_shifts)
+        name, K, n = self.name, self.nframes, self.out_shape[-1]
+        noise_map_path = noise_map_path or None
+        if isinstance(frame_sigmas, str) and frame_sigmas == "":
+            frame_sigmas = None
+        if sum(v is not None for v in (noise_map, noise_map_path, frame_sigmas)) != 1:
+            raise ValueError(f"{name} needs exactly one of noise_map (an array), noise_map_path (a .npy file) and frame_sigmas "
+                             "(one noise level per frame)")
+        if mosaic is not None and not (isinstance(mosaic, str) and mosaic == ""):
+            if not isinstance(mosaic, str) or mosaic.lower() not in BAYER_PATTERNS:
+                raise ValueError(f"{name}: mosaic is None or one of {', '.join(BAYER_PATTERNS)}, got {mosaic!r}")
+            mosaic = mosaic.lower()
+        else:
+            mosaic = None
+        if frame_sigmas is not None:
+            fs = parse_frame_sigmas(frame_sigmas)
+            if fs.size != K:
+                raise ValueError(f"{name}: {fs.size} frame_sigmas for {K} frames; give one noise level per frame")
+            a = np.repeat(fs, 3)[:, None, None] * np.ones((3 * K, n, n))
+        else:
+            a = np.load(noise_map_path) if noise_map is None else \
+                (noise_map.detach().cpu().numpy() if torch.is_tensor(noise_map) else np.asarray(noise_map))
+            shapes = ((n, n), (3, n, n), (K, 3, n, n), (3 * K, n, n), (1, 3 * K, n, n))
+            if tuple(a.shape) not in shapes:
+                raise ValueError(f"{name}: the noise map must have shape " + ", ".join(str(s) for s in shapes[:-1]) +
+                                 f" or {shapes[-1]}, got {tuple(a.shape)}")
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim == 2 or a.shape == (3, n, n):  # one map for every frame ((3, n, n) is also (3 K, n, n) at K = 1: the same)
+                a = np.broadcast_to(a.reshape((1, 1, n, n) if a.ndim == 2 else (1, 3, n, n)), (K, 3, n, n))
+            a = np.ascontiguousarray(a).reshape(3 * K, n, n)
+        self.mosaic = mosaic
+        self._set_burst_noise_map(a)
+
+    def _set_burst_noise_map(self, a):
+        """`_set_noise_map`'s checks, floor and tensors for a [3 K, So, So] array of standard deviations (the mosaic applied)"""
+        name, K, n = self.name, self.nframes, self.out_shape[-1]
+        a = np.array(a, dtype=np.float64).reshape(3 * K, n, n)
+        if np.isnan(a).any():
+            raise ValueError(f"{name}: the noise map has a NaN entry")
+        if not (a > 0).all():
+            raise ValueError(f"{name}: the noise map has an entry <= 0 (entries are standard deviations > 0, or +inf for a "
+                             "pixel that was not measured)")
+        if self.mosaic is not None:
+            a = np.where(np.tile(bayer_sites(n, self.mosaic), (K, 1, 1)), a, np.inf)
+        if np.isinf(a).all():
+            raise ValueError(f"{name}: the noise map is all inf - no pixel is measured")
+        s = a.reshape(1, 3 * K, n, n)
+        s = np.where(np.isinf(s), s, np.maximum(s, self._NOISE_FLOOR))
+        w = np.where(np.isinf(s), 0.0, 1.0 / s)
+        self.noise_map = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)  # float64 [1,3K,So,So]
+        self.weights = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
+        self.mask = (self.weights > 0).to(F64)
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.out_shape[-3:])
+        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`: A^T (mask * v)"""
+        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
+
+
 def _cubic(x):
     ax = np.abs(x)
     return ((1.5 * ax ** 3 - 2.5 * ax ** 2 + 1) * (ax <= 1)

@@ -112,20 +112,23 @@ def main(argv=None):
             op_kw = dict(device=device, sigma_s=o.noise_sigma, kernel_size=o.kernel_size, intensity=o.intensity,
                          scale_factor=o.scale_factor, in_shape=(1, 3, S, S), kernel_path=o.kernel_path or None,
                          mask_path=o.mask_path or None, mask_border=o.mask_border, frame_shifts=o.frame_shifts or None,
+                         frame_sigmas=o.frame_sigmas or None, mosaic=o.mosaic or None,
                          mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
                                    "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
                                    if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})
             img = load_image_u8(files[i], S)
             x_true = enc.encode(img[None].to(device))
-            if o.operator_name in ("weighted_blur", "weighted_sr") and o.noise_gain is not None:
+            clean_name = {"weighted_blur": "custom_blur", "weighted_sr": "custom_sr", "weighted_burst_sr": "burst_sr"}
+            if o.operator_name in clean_name and o.noise_gain is not None:
                 # a Poisson-Gaussian sensor: the measurement is synthesised here with the noise level of the clean signal A0 x,
                 # and the solver gets the map estimated from the measurement itself - what a user with real data would have
-                clean = get_operator(name={"weighted_blur": "custom_blur", "weighted_sr": "custom_sr"}[o.operator_name], **op_kw)
+                clean = get_operator(name=clean_name[o.operator_name], **op_kw)
                 clean.ctx_slot = b
                 ax = clean.forward(x_true, noiseless=True)
                 y = ax + poisson_gaussian_sigma(ax, o.noise_gain, o.noise_read_sigma) * torch.randn_like(ax)
                 op = get_operator(name=o.operator_name, noise_map=poisson_gaussian_sigma(y, o.noise_gain, o.noise_read_sigma),
                                   **op_kw)
+                y = y * op.mask.to(y.dtype)  # (all ones without a mosaic: a raw frame reads 0 off its pattern)
             else:
                 op = get_operator(name=o.operator_name, noise_map_path=o.noise_map_path or None, **op_kw)
                 y = None

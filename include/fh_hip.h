@@ -300,6 +300,17 @@ typedef struct fh_problem {
    * null, fold_sym = 0; use_dct 0 or 1.  The measurement - u, b, x - is [K][3][So][So] per image, n = 3 K So^2 <= 3 S^2.  A solve
    * (and fh_amm) reads the offsets back and checks them once, before its launches.  Anything else: FH_EINVAL before any launch.
    * No p.Ap partials come out of the operator: the CG runs its dot kernel, as for op 2.  K = 1 gives the bits of op 2.
+   * 13 multi-frame super-resolution with a per-pixel noise map: op 12 with the semantics of ops 8 .. 11.  Every field as for op 12
+   * and every refusal of op 12, plus mask != NULL: the WEIGHTS w = 1 / sigma (finite, >= 0, 0 where sigma = inf; validated by the
+   * host) in the measurement's own layout, [K][3][So][So] per image - the weights of frame k, channel c at mask + (3 k + c) So So,
+   * NOT the (p % 3) rule of ops 8 .. 11.  In a batched solve every per->mask[i] is non-null and may differ from image to image.
+   *   fh_amm:   A_mm(u) = sigma_y2 u + W A C A^T W u for an arbitrary u (both sides are applied), = sigma_y2 u exactly where w = 0;
+   *   fh_cg_solve[_batched]: solves for b AS GIVEN, the whitened right-hand side W (y - A x0); mat = A^T W x; sigma_y2 = 1.
+   * The pass that finishes A w writes fma(sigma_y2, u, w * t) with w * t rounded, on either route of fh_conv_frames (the fused
+   * forward kernel in its epilogue, the chain through one streaming pass per frame), so the routes agree bit for bit; all-ones
+   * weights with sigma_y2 = s^2 give the bits of op 12, K = 1 those of op 10.  FH_FRAMES_FUSED is read as for op 12.  mask == NULL
+   * or a null per->mask[i]: FH_EINVAL before any launch and before the offsets are read.  The first such solve of a context
+   * allocates one more CG vector (W p), as for ops 8 .. 11.
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
@@ -314,7 +325,7 @@ typedef struct fh_problem {
   const int32_t* tap_dy; /* [ntaps] */
   const int32_t* tap_dx;
   const double* tap_w;
-  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement); ops 8 .. 11: the weights */
+  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement); ops 8 .. 11 and 13: the weights */
   const double* D;       /* covariance rep: diag, row scale, base, inner matrix */
   const double* r;
   const double* B;
@@ -345,9 +356,9 @@ typedef struct fh_problem {
 } fh_problem;
 
 /* Per-image covariance pointers of a batched solve: B images share the operator, the tap lists, m, ldm and
- * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5, 6 and 8 .. 11 read
- * mask[i], which may differ from image to image (ops 5 / 6 / 8 .. 11: all non-null, else FH_EINVAL; the PSF is shared; ops 8 .. 11
- * also want a non-null fh_problem.mask). */
+ * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5, 6, 8 .. 11 and 13 read
+ * mask[i], which may differ from image to image (ops 5 / 6 / 8 .. 11 / 13: all non-null, else FH_EINVAL; the PSF is shared; ops
+ * 8 .. 11 / 13 also want a non-null fh_problem.mask). */
 #define FH_MAX_BATCH 16
 typedef struct fh_batch {
   int32_t nimg;
