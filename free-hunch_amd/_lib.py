@@ -86,6 +86,9 @@ _SIGS = {
     "fh_conv_frames": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                         C.c_void_p], C.c_int),
     "fh_conv_frames_plan": ([C.c_int] * 7 + [C.POINTER(C.c_int32)], C.c_int),
+    "fh_conv_blend": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, c_dp, C.c_int, C.c_int,
+                       C.c_void_p], C.c_int),
+    "fh_conv_blend_plan": ([C.c_int] * 6 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_conv_window": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_conv_window_plan": ([C.c_int] * 4 + [C.POINTER(C.c_int32)], C.c_int),
     "fh_channel_mix": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_void_p], C.c_int),
@@ -305,6 +308,15 @@ class Context:
         check(self.lib.fh_conv_frames(self.h, ptr(x), ptr(out), ptr(frames.dy), ptr(frames.dx), ptr(frames.w), ptr(frames.off),
                                       frames.nframes, frames.max_taps, frames.halo, planes, stride, int(adjoint), stream()),
               "fh_conv_frames")
+        return out
+
+    def blur_blend(self, x, out, frames, blend, planes, adjoint=False):
+        """The varying-blur operator pair (fh_conv_blend) of a `measurements.FrameTaps` with K PSFs and the blend maps
+        `blend` (float64 [K][3][S][S], shared by the images): x [planes][S][S] -> out [planes][S][S]; float64."""
+        assert blend.dtype == torch.float64 and blend.numel() == frames.nframes * 3 * self.S * self.S
+        check(self.lib.fh_conv_blend(self.h, ptr(x), ptr(out), ptr(frames.dy), ptr(frames.dx), ptr(frames.w), ptr(frames.off),
+                                     frames.nframes, frames.max_taps, frames.halo, ptr(blend), planes, int(adjoint), stream()),
+              "fh_conv_blend")
         return out
 
     def conv(self, x, out, taps, planes, stride=1, adjoint=False):

@@ -66,10 +66,10 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 # (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
 # into rectangular DCT bases op = 7, see _problem; a weighted_blur on the dense-window kernel is op = 9, a weighted_sr on the
 # rectangular bases op = 11; burst_sr is op = 12, the multi-frame operator pair of fh_conv_frames, and weighted_burst_sr is
-# op = 13, the same pair with a noise map on the burst)
+# op = 13, the same pair with a noise map on the burst; varying_blur is op = 14, the blended PSFs of fh_conv_blend)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
             "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10,
-            "burst_sr": 12, "weighted_burst_sr": 13}
+            "burst_sr": 12, "weighted_burst_sr": 13, "varying_blur": 14}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
 # operators whose PSF is the caller's: a lock-step batch must share it
 _SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr")
@@ -81,7 +81,7 @@ _WEIGHTED = ("weighted_blur", "weighted_sr", "weighted_burst_sr")
 _BURST = ("burst_sr", "weighted_burst_sr")
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
                  "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'. Also 'burst_sr' and "
-                 "'weighted_burst_sr'.")
+                 "'weighted_burst_sr'. Also 'varying_blur'.")
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -119,6 +119,14 @@ def _problem(operator, cov, sigma_y2):
             w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
             p.mask = w.data_ptr()
             keep.append(w)
+        return p, keep
+    if operator.name == "varying_blur":  # op 14: the PSFs' tap lists as for the frames, the blend maps [K, 3, S, S] in tap2_w
+        ft = operator.frame_taps
+        blend = operator.blend.to(device=cov.device, dtype=F64).contiguous()
+        p.ntaps, p.halo = ft.n, ft.halo
+        p.tap_dy, p.tap_dx, p.tap_w = ft.dy.data_ptr(), ft.dx.data_ptr(), ft.w.data_ptr()
+        p.ntaps2, p.halo2, p.tap2_dy, p.tap2_w = ft.nframes, ft.max_taps, ft.off.data_ptr(), blend.data_ptr()
+        keep.extend([ft.dy, ft.dx, ft.w, ft.off, blend])
         return p, keep
     if operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
@@ -243,6 +251,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     # has joined its per-image streams) -> the covariance apply inside CG reads each factor base once, not twice
     ctx.set_exclusive(exclusive)
     prob, keep = _problem(op0, cov0, _solver_sigma_y2(op0))
+    blend = keep[-1] if name == "varying_blur" else None  # op 14: _problem keeps the device blend maps last
     per = _lib.FhBatch()
     per.nimg = B
     m = cov0.famC.m
@@ -259,6 +268,12 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             assert op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in
                                                      zip(op.kernels, op0.kernels)), \
                 "lock-step images must share the PSF of every frame"
+        if name == "varying_blur":
+            assert op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in
+                                                     zip(op.kernels, op0.kernels)), \
+                "lock-step images must share every PSF"
+            assert op.blend.shape == op0.blend.shape and torch.equal(op.blend, op0.blend), \
+                "lock-step images must share the blend maps"
         if name in _DECIMATING:
             assert op.scale_factor == op0.scale_factor, "lock-step images must share the scale_factor"
         if name in _MASKED or name == "masked_blur":
@@ -280,6 +295,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             out = torch.empty(B, 3 if adjoint else 3 * op0.nframes, so, so, dtype=F64, device=dev)
             return ctx.blur_frames(v, out, op0.frame_taps, planes, prob.stride, adjoint)
         out = torch.empty(B, 3, so, so, dtype=F64, device=dev)
+        if name == "varying_blur":  # the blended PSFs, the maps shared by the images
+            return ctx.blur_blend(v, out, op0.frame_taps, blend, planes, adjoint)
         return ctx.blur(v, out, op0.taps, planes, prob.stride, adjoint)
 
     def mix(v, adjoint):

@@ -67,6 +67,10 @@ SCHEMA = {
     # [1,3K,So,So]), --frame_sigmas="a,b,c,..." (one level per frame, inf drops a frame) and the sensor pair --noise_gain /
     # --noise_read_sigma; --mosaic=rggb | bggr | grbg | gbrg makes every frame a raw Bayer frame (one channel per site)
     "frame_sigmas": (str, ""), "mosaic": (str, ""),
+    # NEW: --operator_name=varying_blur, a PSF that changes across the field: --kernel_path holds a [K, kh, kw] array of PSFs
+    # (K <= 16) and exactly one of --blend_path (a .npy of blend maps [K,S,S], [K,3,S,S] or [3K,S,S]) and --psf_grid=RxC (the
+    # PSFs on an R x C grid, R * C = K, blended bilinearly between the cell centres: measurements.grid_blend_weights)
+    "blend_path": (str, ""), "psf_grid": (str, ""),
 }
 
 
@@ -105,6 +109,15 @@ def load_config(argv=None):
     if cfg["operator_name"] in ("burst_sr", "weighted_burst_sr") and not cfg["kernel_path"]:
         raise SystemExit(f"--operator_name={cfg['operator_name']} needs --kernel_path=FILE.npy (a [K, kh, kw] array of per-frame PSFs, or one 2-D "
                          "PSF beside --frame_shifts) beside --scale_factor")
+    if cfg["operator_name"] == "varying_blur":
+        if not cfg["kernel_path"]:
+            raise SystemExit("--operator_name=varying_blur needs --kernel_path=FILE.npy (a [K, kh, kw] array of PSFs)")
+        if bool(cfg["blend_path"]) == bool(cfg["psf_grid"]):
+            raise SystemExit("--operator_name=varying_blur needs its blend maps: exactly one of --blend_path=FILE.npy and "
+                             "--psf_grid=RxC")
+    elif cfg["blend_path"] or cfg["psf_grid"]:
+        raise SystemExit(f"--blend_path and --psf_grid belong to --operator_name=varying_blur; operator "
+                         f"'{cfg['operator_name']}' does not read them")
     if cfg["frame_shifts"] and cfg["operator_name"] not in ("burst_sr", "weighted_burst_sr"):
         raise SystemExit(f"--frame_shifts belongs to --operator_name=burst_sr (and weighted_burst_sr); operator "
                          f"'{cfg['operator_name']}' does not read it")
@@ -134,8 +147,8 @@ def load_config(argv=None):
         raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
     if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr", "weighted_blur",
-                                                           "weighted_sr", "burst_sr", "weighted_burst_sr"):
+                                                           "weighted_sr", "burst_sr", "weighted_burst_sr", "varying_blur"):
         raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr / weighted_blur / "
-                         f"weighted_sr / burst_sr / weighted_burst_sr; operator "
+                         f"weighted_sr / burst_sr / weighted_burst_sr / varying_blur; operator "
                          f"'{cfg['operator_name']}' does not read it")
     return SimpleNamespace(**cfg)

@@ -2312,6 +2312,113 @@ __global__ __launch_bounds__(256) void k_conv_up_frames(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// Spatially varying blur (fh_problem.op = 14, fh_conv_blend): the Nagy-O'Leary interpolation of K shift-invariant blurs,
+//   A = sum_k diag(U_k) B_k,   A^T = sum_k B_k^T diag(U_k),
+// B_k the stride-1 circular blur of tap list k (lists concatenated, foff[K + 1] their offsets, as for op 12) and U_k a
+// per-pixel blend map, blend[K][3][S][S], shared by every image (the map of frame k for plane p at (3 k + p % 3) S S).
+// One kernel, k_conv_blend<NR, ADJ>, on a 32 x 8 NR output tile, a thread = NR outputs 8 rows apart (k_conv_tile's layout at
+// NR = 2, k_conv_tile8's footprint at NR = 8); the frames take turns in the tap staging (cap_taps pairs), as in
+// conv_dec_frames_body:
+//   ADJ = 0 : the input tile is staged ONCE for the union of the extents; per frame t_k = one fma chain from 0 in list order,
+//             then the epilogue blends in frame order, tot = fma(add_scale, add, U_0 t_0) (U_0 t_0 without add), then
+//             tot = fma(1, tot, U_k t_k), every product U_k t_k rounded - the bits of K conv_launch + k_mask passes.
+//   ADJ = 1 : the tile is re-staged per frame as the rounded product U_k .* in (the input itself comes through L2, so the
+//             LDS holds one tile, not two); per frame one fma chain from 0, the frames added in index order, one rounding
+//             each - the bits of K k_mask + conv_launch passes chained through add (add_scale = 1).
+// Edge guards as k_conv_tile: any even S tiles.  A frame's taps are read inside [0, ntaps) and at most cap_taps of them
+// whatever foff holds (the host has checked foff, frames_prepare); the tile indices trust hy / hx.  No atomics.
+// ------------------------------------------------------------------------------------------------
+struct conv_blend_lds {  // [sh][sw] tile (+1 to an even count) | [cap_taps] (weight, offset) pairs
+  int sw, sh, tap_off;
+  size_t bytes;
+  __host__ __device__ conv_blend_lds(int nr, int hy, int hx, int cap_taps)
+      : sw(32 + 2 * hx), sh(8 * nr + 2 * hy), tap_off((sw * sh + 1) & ~1),
+        bytes((size_t)tap_off * sizeof(double) + (size_t)cap_taps * 16) {}
+};
+
+// a product that stays a product: rounded before whatever adds to it (no contraction into the blend's fma)
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+  const double p = a * b;
+  return p;
+}
+
+template <int NR, bool ADJ>
+__global__ __launch_bounds__(256) void k_conv_blend(const double* __restrict__ in, double* __restrict__ out,
+                                                    const int* __restrict__ tdy, const int* __restrict__ tdx,
+                                                    const double* __restrict__ tw, const int* __restrict__ foff, int K,
+                                                    int ntaps, int cap_taps, int S, int hy, int hx,
+                                                    const double* __restrict__ blend, const double* __restrict__ add,
+                                                    double add_scale, const fh_cg_state* __restrict__ states) {
+  IMG_GUARD(states, blockIdx.z / 3);
+  extern __shared__ __align__(16) double tile[];
+  const conv_blend_lds L(NR, hy, hx, cap_taps);
+  const int sw = L.sw, sh = L.sh;
+  double2* s_tap = reinterpret_cast<double2*>(tile + L.tap_off);
+  const int plane = blockIdx.z, ch = plane % 3;
+  const int oy0 = blockIdx.y * (8 * NR), ox0 = blockIdx.x * 32;
+  const int64_t SS = (int64_t)S * S;
+  const double* src = in + (int64_t)plane * SS;
+  const int sgn = ADJ ? 1 : -1;
+  const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;  // rows ly + 8 r
+  const double* q = tile + (ly + hy) * sw + lx + hx;
+  const int ox = ox0 + lx;
+  double tot[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) tot[r] = 0.0;
+  for (int k = 0; k < K; ++k) {
+    int t0, n;
+    frame_range(foff, k, ntaps, &t0, &n);
+    n = n < cap_taps ? n : cap_taps;
+    const double* uk = blend + (int64_t)(3 * k + ch) * SS;
+    if (k > 0) __syncthreads();  // the previous frame's pairs (and, ADJ, its tile) have been read
+    for (int t = threadIdx.x; t < n; t += 256)
+      s_tap[t] = make_double2(tw[t0 + t], __longlong_as_double((long long)(sgn * (tdy[t0 + t] * sw + tdx[t0 + t]))));
+    if (ADJ || k == 0) {
+      for (int ty = threadIdx.x >> 6; ty < sh; ty += 4) {  // a wave per tile row: no division by the run-time row pitch
+        int gy = (oy0 + ty - hy) % S;
+        gy += gy < 0 ? S : 0;
+        const double* srow = src + (int64_t)gy * S;
+        const double* urow = uk + (int64_t)gy * S;
+        for (int tx = threadIdx.x & 63; tx < sw; tx += 64) {
+          int gx = (ox0 + tx - hx) % S;
+          gx += gx < 0 ? S : 0;
+          tile[ty * sw + tx] = ADJ ? mul_rounded(urow[gx], srow[gx]) : srow[gx];
+        }
+      }
+    }
+    __syncthreads();
+    double acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.0;
+#pragma unroll 2
+    for (int t = 0; t < n; ++t) {
+      const double2 tp = s_tap[t];
+      const double* p = q + (int)__double_as_longlong(tp.y);
+#pragma unroll
+      for (int r = 0; r < NR; ++r) acc[r] = fma(tp.x, p[r * 8 * sw], acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int oy = oy0 + ly + 8 * r;
+      if (ADJ) {
+        tot[r] = k == 0 ? acc[r] : fma(1.0, tot[r], acc[r]);
+      } else if (oy < S && ox < S) {
+        const double t = mul_rounded(uk[(int64_t)oy * S + ox], acc[r]);
+        if (k > 0) tot[r] = fma(1.0, tot[r], t);
+        else tot[r] = add != nullptr ? fma(add_scale, add[(int64_t)plane * SS + (int64_t)oy * S + ox], t) : t;
+      }
+    }
+  }
+  if (ox >= S) return;
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    const int oy = oy0 + ly + 8 * r;
+    if (oy < S) out[(int64_t)plane * SS + (int64_t)oy * S + ox] = tot[r];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The m x m part of a Woodbury step / forward time shift on the device (online_update_bfgs.py:87-119 in the real form of
 // this build):   Mdst = sym( sign * Msrc (I + alpha G Msrc)^-1 ),   (alpha, sign) = (1, -1): Woodbury inverse; (s, +1): shift.
 // One workgroup, matrices in LDS.  A = I + alpha G Msrc is NOT well conditioned: the factor columns of a trajectory are
@@ -2874,6 +2981,100 @@ static int frames_launch(fh_context* ctx, const double* in, double* out, const i
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The launch plan of fh_conv_blend (fh_conv_blend_plan reports it), pure host arithmetic like frames_plan.  Two routes:
+//   fused : ONE k_conv_blend launch over all frames and planes: the 32 x 64 tile (NR = 8) where its LDS for the union extents,
+//           with the tap staging sized for the longest frame, fits the default 64 KiB, else the 32 x 16 tile (NR = 2) inside
+//           the opt-in (76 KiB at hy = hx = 32 with 1024 taps: it always fits, so the plan never refuses by LDS size);
+//   chain : per frame one conv_launch over all planes and one k_mask over all images (the blend maps are shared by the images)
+//           through a spare work vector, which fixes the arithmetic (see k_conv_blend).  Its kernels hold at most 64 KiB, so
+//           at wide extents with long lists only the fused route exists, and it then runs whatever the switch says.
+// The plan reports the fused launch: it exists for every legal argument, and it is the default by measurement
+// (profiles/varying_blur.md).
+// ------------------------------------------------------------------------------------------------
+struct blend_choice {  // the fused launch, and whether the chain exists beside it
+  int chain_ok, nr;
+  dim3 grid;
+  size_t lds;
+  int hy, hx;
+};
+
+static int blend_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int adjoint, blend_choice* c) {
+  if (S < 2 || S > 256 || (S & 1) || nframes < 1 || nframes > 16) return FH_EINVAL;
+  if (max_frame_taps < 1 || max_frame_taps > kMaxTaps) return FH_EINVAL;
+  if (planes < 3 || planes % 3 != 0 || halo < 1000 || (adjoint != 0 && adjoint != 1)) return FH_EINVAL;
+  conv_extent e;
+  const int rc = conv_decode(halo, &e);
+  if (rc) return rc;
+  *c = {0, 0, dim3(1), 0, e.hy, e.hx};
+  if (planes > 65535) return FH_ESIZE;  // (the plane is grid dimension z)
+  conv_choice one;
+  c->chain_ok = conv_plan(S, max_frame_taps, e, planes, 1, adjoint, &one) == 0;
+  // the largest NR = 2 layout (extents 32, kMaxTaps pairs) is 76 KiB: the fused kernel has a launch for every legal argument
+  static_assert(96 * 80 * sizeof(double) + kMaxTaps * 16 <= kLdsOptIn, "k_conv_blend<2> must fit the opt-in at the widest extents");
+  c->nr = conv_blend_lds(8, e.hy, e.hx, max_frame_taps).bytes <= kLdsDefault ? 8 : 2;
+  c->lds = conv_blend_lds(c->nr, e.hy, e.hx, max_frame_taps).bytes;
+  c->grid = dim3((unsigned)((S + 31) / 32), (unsigned)((S + 8 * c->nr - 1) / (8 * c->nr)), (unsigned)planes);
+  return 0;
+}
+
+// FH_BLEND_FUSED=0: the chain also where the fused kernel fits (A/B switch, like FH_FRAMES_FUSED).  Read at every op 14 /
+// fh_conv_blend call (and by no other op); the CG graph cache keys on it for op 14.
+static bool blend_fused_on() {
+  const char* v = getenv("FH_BLEND_FUSED");
+  return v == nullptr || atoi(v) != 0;
+}
+// the route a launch takes: the switch decides only where both routes exist
+static bool blend_route_fused(const blend_choice& c) { return blend_fused_on() || !c.chain_ok; }
+
+// in [planes][S][S] -> out [planes][S][S]: out = add_scale * add + sum_k U_k .* conv(in; list k), or with `adjoint`
+// out = sum_k conv^T(U_k .* in; list k) (no add).  frames_prepare has run for these offsets.  `spare`: a work vector of the
+// caller's ([planes][S][S], not in / out / add) for the chain.
+static int blend_launch(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx, const double* w,
+                        const int32_t* frame_off, int ntaps, int nframes, int max_frame_taps, int halo, int planes,
+                        int adjoint, const double* blend, const double* add, double add_scale, const fh_cg_state* done,
+                        hipStream_t st, double* spare) {
+  const int S = ctx->S;
+  blend_choice c;
+  const int rc = blend_plan(S, nframes, max_frame_taps, halo, planes, adjoint, &c);
+  if (rc) return rc;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  if (blend == nullptr || spare == nullptr || planes / 3 > FH_MAX_BATCH) return FH_EINVAL;
+  if (blend_route_fused(c)) {
+    const auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, c.grid, dim3(256), c.lds, st, in, out, dy, dx, w, frame_off, nframes, ntaps, max_frame_taps, S,
+                         c.hy, c.hx, blend, adjoint ? (const double*)nullptr : add, add_scale, done);
+    };
+    if (c.nr == 8) adjoint ? go(k_conv_blend<8, true>) : go(k_conv_blend<8, false>);
+    else adjoint ? go(k_conv_blend<2, true>) : go(k_conv_blend<2, false>);
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
+  const int nimg = planes / 3;
+  const int64_t n = (int64_t)3 * S * S;
+  const dim3 mgrid(512, 1, (unsigned)nimg);
+  for (int k = 0; k < nframes; ++k) {
+    const int t0 = ctx->frame_off[k], nk = ctx->frame_off[k + 1] - t0;
+    fh_batch uk;  // the maps of frame k as k_mask's per-image table: every image reads the same three planes
+    memset(&uk, 0, sizeof(uk));
+    uk.nimg = nimg;
+    for (int i = 0; i < nimg; ++i) uk.mask[i] = blend + (int64_t)k * n;
+    int rc2;
+    if (adjoint) {
+      hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, uk, in, (const double*)nullptr, 0.0, spare, n, done);
+      rc2 = conv_launch(ctx, spare, out, dy + t0, dx + t0, w + t0, nk, halo, planes, 1, 1, k > 0 ? out : nullptr, 1.0, done, st);
+    } else {
+      rc2 = conv_launch(ctx, in, spare, dy + t0, dx + t0, w + t0, nk, halo, planes, 1, 0, nullptr, 0.0, done, st);
+      if (rc2) return rc2;
+      hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, uk, (const double*)spare, k > 0 ? (const double*)out : add,
+                         k > 0 ? 1.0 : add_scale, out, n, done);
+    }
+    if (rc2) return rc2;
+  }
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
 // The launch plan of fh_conv_window (fh_conv_window_plan reports it): one kernel, its grid and its LDS from conv_window_lds.
 static int window_plan(int S, int hy, int hx, int planes, dim3* grid, size_t* lds) {
   if (S < 2 || S > 256 || (S & 1) || hy < 0 || hy > 32 || hx < 0 || hx > 32 || planes < 1) return FH_EINVAL;
@@ -2918,7 +3119,18 @@ static int window_problem_check(const fh_problem* p) {
 // (the masks of a batched solve are per->mask[i]: masks_check)
 // S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 13) return FH_EINVAL;
+  if (p->op < 0 || p->op > 14) return FH_EINVAL;
+  if (p->op == 14) {  // varying blur: ntaps2 = K PSFs, tap2_dy = their offsets, halo2 = the longest list, tap2_w = the blend maps
+    const int K = p->ntaps2;
+    conv_extent e;
+    if (p->stride != 1 || K < 1 || K > 16 || (p->use_dct != 0 && p->use_dct != 1)) return FH_EINVAL;
+    if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
+    if (p->halo < 1000 || conv_decode(p->halo, &e) != 0) return FH_EINVAL;
+    if (!p->tap2_dy || !p->tap2_w || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
+    if (p->tap2_dx || p->mask || p->fold_sym != 0) return FH_EINVAL;
+    if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
+    return 0;
+  }
   if (p->op == 12 || p->op == 13) {  // multi-frame SR: stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
     // (op 13 brings the weights in mask: masks_check refuses a null one)
     const int s = p->stride, K = p->ntaps2;
@@ -2948,13 +3160,16 @@ static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
 static bool weighted_op(const fh_problem* p) { return (p->op >= 8 && p->op <= 11) || p->op == 13; }
 // ops 12 / 13 (multi-frame SR): ntaps2 counts frames, tap2_dy holds their offsets
 static bool frames_op(const fh_problem* p) { return p->op == 12 || p->op == 13; }
+// op 14 (varying blur): ntaps2 counts PSFs and tap2_dy holds their offsets as for the frames, but the measurement keeps the
+// image's size and nothing decimates
+static bool blend_op(const fh_problem* p) { return p->op == 14; }
 static bool decimating_op(const fh_problem* p) {
   return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || frames_op(p);
 }
 // measurement planes per image: one for colorization, 3 K for the K frames of ops 12 / 13, else 3
 static int meas_planes(const fh_problem* p) { return p->op == 3 ? 1 : (frames_op(p) ? p->ntaps2 : 1) * p->planes; }
 static int masks_check(const fh_problem* p, const fh_batch& per) {
-  if (p->op == 7 || p->op == 12) {  // no mask on the low-resolution measurement
+  if (p->op == 7 || p->op == 12 || p->op == 14) {  // no mask on the low-resolution measurement, none on the varying blur
     for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
       if (per.mask[i] != nullptr) return FH_EINVAL;
     return 0;
@@ -3102,7 +3317,8 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
   const bool frames = frames_op(p);               // multi-frame SR: ntaps2 counts frames, tap2_dy holds their offsets
-  const bool sep = !frames && p->ntaps2 > 0;      // separable PSF: two 1-D passes (blur only, stride 1)
+  const bool blend = blend_op(p);                 // varying blur: the same two fields, and the maps in tap2_w
+  const bool sep = !frames && !blend && p->ntaps2 > 0;  // separable PSF: two 1-D passes (blur only, stride 1)
   if (sep && p->stride != 1) return FH_EINVAL;
   if (blur && p->use_dct && p->fold_fwd_w != nullptr) {
     // separable blur folded into the DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in 4 dense passes + the
@@ -3148,6 +3364,10 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     rc = frames_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
                        p->stride, 1, nullptr, 0.0, states, st);
     if (rc) return rc;
+  } else if (blend) {
+    rc = blend_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes, 1,
+                      p->tap2_w, nullptr, 0.0, states, st, w1);  // (w1 is free until the covariance apply: the chain's spare)
+    if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, uin, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
                      states, st);
@@ -3187,6 +3407,10 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
   } else if (frames) {
     rc = frames_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
                        p->stride, 0, u, p->sigma_y2, states, st, masks, w0);  // (op 13: w0 is the spare, as below)
+    if (rc) return rc;
+  } else if (blend) {
+    rc = blend_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes, 0,
+                      p->tap2_w, u, p->sigma_y2, states, st, w0);  // (w0 has been read: the chain's spare)
     if (rc) return rc;
   } else if (sep) {
     rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
@@ -3412,7 +3636,9 @@ static int set_kernel_attributes() {
                                  (const void*)k_woodbury_inner,       (const void*)k_dct_rect<3>};
   for (const void* fn : at_140k) FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
   for (const void* fn : {(const void*)k_conv_dec, (const void*)k_conv_up, (const void*)k_conv_dec_frames,
-                         (const void*)k_conv_dec_frames_w, (const void*)k_conv_up_frames})
+                         (const void*)k_conv_dec_frames_w, (const void*)k_conv_up_frames,
+                         (const void*)k_conv_blend<8, false>, (const void*)k_conv_blend<8, true>,
+                         (const void*)k_conv_blend<2, false>, (const void*)k_conv_blend<2, true>})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsOptIn));
   for (const void* fn : {(const void*)k_conv_window, (const void*)k_conv_window_masked})
     FH_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsWindow));
@@ -4013,6 +4239,33 @@ int fh_conv_frames_plan(int S, int nframes, int max_frame_taps, int halo, int pl
   return 0;
 }
 
+int fh_conv_blend(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx, const double* w,
+                  const int32_t* frame_off, int nframes, int max_frame_taps, int halo, const double* blend, int planes,
+                  int adjoint, void* stream) {
+  if (!ctx || !in || !out || !dy || !dx || !w || !frame_off || !blend || in == out) return FH_EINVAL;
+  blend_choice c;
+  int rc = blend_plan(ctx->S, nframes, max_frame_taps, halo, planes, adjoint, &c);  // every argument, before the copy below
+  if (rc) return rc;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  if (planes / 3 > FH_MAX_BATCH) return FH_EINVAL;
+  int ntaps = -1;  // the total tap count is the last offset: one read of all K + 1
+  rc = frames_prepare(ctx, frame_off, nframes, &ntaps, max_frame_taps, (hipStream_t)stream);
+  if (rc) return rc;
+  return blend_launch(ctx, in, out, dy, dx, w, frame_off, ntaps, nframes, max_frame_taps, halo, planes, adjoint, blend, nullptr,
+                      0.0, nullptr, (hipStream_t)stream, ctx->w0);  // (a work vector, idle outside fh_amm / a solve)
+}
+
+int fh_conv_blend_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int adjoint, int32_t out[6]) {
+  if (out == nullptr) return FH_EINVAL;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  blend_choice c;
+  const int rc = blend_plan(S, nframes, max_frame_taps, halo, planes, adjoint, &c);
+  if (rc) return rc;
+  const int32_t v[6] = {1, (int32_t)c.grid.x, (int32_t)c.grid.y, (int32_t)c.grid.z, 256, (int32_t)c.lds};
+  memcpy(out, v, sizeof(v));
+  return 0;
+}
+
 int fh_conv_window(fh_context* ctx, const double* in, double* out, const double* win, int hy, int hx, int planes, int adjoint,
                    void* stream) {
   if (!ctx || !in || !out || !win || in == out) return FH_EINVAL;
@@ -4055,7 +4308,8 @@ int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, v
   if (masks_check(p, per)) return FH_EINVAL;
   const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
   if (rc) return rc;
-  if (frames_op(p)) {  // (before the first launch of op 13 as well)
+  if (frames_op(p) || blend_op(p)) {  // (before the first launch of op 13 as well)
+    if (blend_op(p) && (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3)) return FH_EINVAL;
     int total = p->ntaps;
     const int rcf = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, (hipStream_t)stream);
     if (rcf) return rcf;
@@ -4114,11 +4368,12 @@ static hipGraphExec_t cg_graph_for(fh_context* ctx, const fh_problem* p, const f
   // ops 12 / 13: the chain route bakes host-sliced tap pointers and counts into the graph, so the route switch and the offsets
   // that frames_prepare has just checked (ctx->frame_off) belong to the key; other ops never read the switch.  (The weights'
   // pointers of op 13 are part of bkey, like those of ops 8 .. 11; their values are read by the kernels at every replay.)
-  const int frames_route = frames_op(p) ? (int)frames_fused_on() : 0;
+  const bool offsets_op = frames_op(p) || blend_op(p);  // op 14: the same, with its own switch (FH_BLEND_FUSED)
+  const int frames_route = frames_op(p) ? (int)frames_fused_on() : (blend_op(p) ? (int)blend_fused_on() : 0);
   fh_graph_entry* slot = &ctx->graphs[0];
   for (auto& g : ctx->graphs) {
     if (g.exec != nullptr && g.n == n && memcmp(&g.key, p, sizeof(fh_problem)) == 0 &&
-        (!frames_op(p) || (g.frames_fused == frames_route && memcmp(g.frame_off, ctx->frame_off, sizeof(g.frame_off)) == 0)) &&
+        (!offsets_op || (g.frames_fused == frames_route && memcmp(g.frame_off, ctx->frame_off, sizeof(g.frame_off)) == 0)) &&
         memcmp(&g.bkey, &per, sizeof(fh_batch)) == 0) {
       g.stamp = ctx->graph_clock;
       return g.exec;
@@ -4189,7 +4444,7 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
     if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
   int rc = colorize_prepare(ctx, p, per, st);
   if (rc) return rc;
-  if (frames_op(p)) {  // the frame offsets, read and checked once per solve (the chain route launches from the host copy)
+  if (frames_op(p) || blend_op(p)) {  // the offsets, read and checked once per solve (the chain route launches from the host copy)
     if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
     int total = p->ntaps;
     rc = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, st);

@@ -640,6 +640,179 @@ class BurstSROperator(LinearOperator):
         return None  # (a rank-1 fold of the frames into rectangular bases is not built)
 
 
+def grid_blend_weights(S, rows, cols):
+    """Blend maps of a rows x cols grid of PSFs over an S x S image, float64 [rows * cols, S, S], row-major over the grid:
+    the tensor product of 1-D hat functions whose nodes sit at the cell centres (i + 0.5) S / n (pixel j at coordinate
+    j + 0.5).  Beyond the outermost nodes a map stays constant - no wrap-around - and a grid of one node along an axis is all
+    ones along it.  Every pixel's weights sum to 1 (a partition of unity; within 1e-15)."""
+    S, rows, cols = int(S), int(rows), int(cols)
+    if S < 1 or rows < 1 or cols < 1:
+        raise ValueError(f"grid_blend_weights: S, rows and cols must be positive, got {S}, {rows}, {cols}")
+
+    def hats(n):
+        """[n, S]: hat i is 1 at node i and falls to 0 at its neighbours; clamped outside the first / last node"""
+        if n == 1:
+            return np.ones((1, S))
+        nodes = (np.arange(n) + 0.5) * S / n
+        t = np.clip((np.arange(S) + 0.5 - nodes[0]) / (nodes[1] - nodes[0]), 0.0, n - 1.0)  # position in node units
+        lo = np.minimum(np.floor(t).astype(np.int64), n - 2)  # the pixel's cell: at most two hats are non-zero, 1 - f and f
+        f = t - lo
+        h = np.zeros((n, S))
+        h[lo, np.arange(S)] = 1.0 - f
+        h[lo + 1, np.arange(S)] += f
+        return h
+
+    hy, hx = hats(rows), hats(cols)
+    return np.ascontiguousarray((hy[:, None, :, None] * hx[None, :, None, :]).reshape(rows * cols, S, S))
+
+
+def parse_psf_grid(grid):
+    """`psf_grid` as (rows, cols): a pair of positive integers, or the command line's "RxC" string"""
+    try:
+        if isinstance(grid, str):
+            r, c = grid.lower().split("x")
+            rows, cols = int(r), int(c)
+        else:
+            rows, cols = (int(v) for v in grid)
+            if tuple(float(v) for v in grid) != (rows, cols):
+                raise ValueError
+    except (ValueError, TypeError):
+        raise ValueError(f"varying_blur: psf_grid is (rows, cols) or the string 'RxC' with positive integers, got {grid!r}") from None
+    if rows < 1 or cols < 1:
+        raise ValueError(f"varying_blur: psf_grid is (rows, cols) or the string 'RxC' with positive integers, got {grid!r}")
+    return rows, cols
+
+
+@register_operator(name="varying_blur")
+class VaryingBlurOperator(LinearOperator):
+    """Blur with a PSF that changes across the field, as the Nagy-O'Leary interpolation of K shift-invariant blurs:
+        y = sum_k U_k .* (B_k x) + sigma_s n,   A = sum_k diag(U_k) B_k,   A^T = sum_k B_k^T diag(U_k),
+    B_k the circular blur of `custom_blur` with PSF k (centre at index size // 2, rounded to float32, used as given) and U_k a
+    per-pixel blend map.  1 <= K <= 16; the measurement keeps the image's size.
+      kernels       K 2-D arrays (or a [K, kh, kw] array)
+      kernel_path   a .npy with a [K, kh, kw] array (or one 2-D PSF: K = 1)
+      blend         an array or tensor [K, S, S] (broadcast over the channels), [K, 3, S, S] or [3 K, S, S] (channel 3 k + c)
+      blend_path    a .npy of the same
+      psf_grid      (rows, cols) or "RxC" with rows * cols = K: the maps of `grid_blend_weights`, the PSFs row-major on the grid
+    Exactly one of kernels / kernel_path and exactly one of blend / blend_path / psf_grid.  The maps must be finite and none may
+    be all zero; a partition of unity is NOT enforced: any finite maps are a valid linear A (maps that do not sum to one change
+    the local gain, negative entries are allowed).  `forward` and `transpose` are one A (fh_conv_blend); the solver's system is
+    fh_problem.op = 14.  Every PSF has at most `Taps.MAX_TAPS` non-zeros and reaches at most 32 from its centre."""
+
+    MAX_PSFS = 16
+
+    def __init__(self, in_shape, sigma_s, device, kernels=None, kernel_path=None, blend=None, blend_path=None, psf_grid=None,
+                 **kwargs):
+        S = int(in_shape[-1])
+        if (kernel_path is None or kernel_path == "") == (kernels is None):
+            raise ValueError("varying_blur needs exactly one of kernels (K 2-D arrays) and kernel_path (a .npy file with a "
+                             "[K, kh, kw] array)")
+        if kernels is None:
+            arr = np.load(kernel_path)
+            if arr.ndim not in (2, 3):
+                raise ValueError(f"varying_blur: {kernel_path} must hold a [K, kh, kw] array or one 2-D PSF, got shape {tuple(arr.shape)}")
+            psfs = [arr] if arr.ndim == 2 else list(arr)
+        else:
+            psfs = [kernels] if (isinstance(kernels, np.ndarray) and kernels.ndim == 2) else list(kernels)
+        psfs = [np.asarray(k, dtype=np.float64) for k in psfs]
+        if not psfs or any(k.ndim != 2 or k.size == 0 for k in psfs):
+            raise ValueError("varying_blur: every PSF must be a non-empty 2-D array")
+        K = len(psfs)
+        if not 1 <= K <= self.MAX_PSFS:
+            raise ValueError(f"varying_blur: {K} PSFs; the number of PSFs K is 1 .. {self.MAX_PSFS}")
+        given = [blend is not None, not (blend_path is None or blend_path == ""), not (psf_grid is None or psf_grid == "")]
+        if sum(given) != 1:
+            raise ValueError("varying_blur needs exactly one of blend (an array [K, S, S], [K, 3, S, S] or [3 K, S, S]), "
+                             "blend_path (a .npy file of the same) and psf_grid ((rows, cols) or 'RxC')")
+        if given[2]:
+            rows, cols = parse_psf_grid(psf_grid)
+            if rows * cols != K:
+                raise ValueError(f"varying_blur: psf_grid {rows} x {cols} holds {rows * cols} nodes for {K} PSFs; rows * cols must be K")
+            maps = grid_blend_weights(S, rows, cols)
+        elif given[1]:
+            maps = np.load(blend_path)
+        else:
+            maps = blend.detach().cpu().numpy() if isinstance(blend, torch.Tensor) else np.asarray(blend)
+        maps = np.asarray(maps, dtype=np.float64)
+        if tuple(maps.shape) == (K, S, S):
+            maps = np.broadcast_to(maps[:, None], (K, 3, S, S))
+        elif tuple(maps.shape) in ((K, 3, S, S), (3 * K, S, S)):
+            maps = maps.reshape(K, 3, S, S)
+        else:
+            raise ValueError(f"varying_blur: the blend maps must have shape [{K}, {S}, {S}], [{K}, 3, {S}, {S}] or [{3 * K}, {S}, {S}] "
+                             f"for {K} PSFs on a {S} x {S} image, got {tuple(maps.shape)}")
+        if not np.isfinite(maps).all():
+            raise ValueError("varying_blur: the blend maps have a non-finite entry")
+        for i in range(K):
+            if not maps[i].any():
+                raise ValueError(f"varying_blur: the blend map of PSF {i} is all zero (drop the PSF instead)")
+        self.device = torch.device(device)
+        self.frames, self.kernels = [], []
+        for i, k in enumerate(psfs):
+            with np.errstate(over="ignore"):
+                k = np.asarray(k, dtype=np.float32)
+            if not np.isfinite(k).all():
+                raise ValueError(f"varying_blur: PSF {i} has a non-finite entry (also after rounding to float32)")
+            if not k.any():
+                raise ValueError(f"varying_blur: PSF {i} is all zero")
+            ys, xs = np.nonzero(k)
+            hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
+            if max(hy, hx) > 32:
+                raise ValueError(f"varying_blur: PSF {i} reaches ({hy}, {hx}) samples from its centre at index size // 2; the "
+                                 "kernels stage at most 32 (PSFs up to 65 x 65)")
+            if ys.size > Taps.MAX_TAPS:
+                raise ValueError(f"varying_blur: PSF {i} has {ys.size} non-zeros, a tap list holds {Taps.MAX_TAPS}")
+            self.kernels.append(k)
+            self.frames.append(Taps(k, self.device))
+        self.frame_taps = FrameTaps(self.frames, self.device)
+        import ctypes
+        plan, out = _lib.load().fh_conv_blend_plan, (ctypes.c_int32 * 6)()
+        ft = self.frame_taps
+        for adjoint in (0, 1):
+            rc = plan(S, K, ft.max_taps, ft.halo, 3, adjoint, out)
+            if rc != 0:
+                raise ValueError(f"varying_blur: no kernel runs these tap lists (at most {ft.max_taps} taps per PSF reaching "
+                                 f"({ft.hy}, {ft.hx})) on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
+        self.nframes = K
+        self.blend = torch.from_numpy(np.ascontiguousarray(maps)).to(self.device)  # float64 [K, 3, S, S]
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
+        self.out_shape = in_shape
+
+    def _conv(self, x, stride=None, adjoint=False):
+        """A (or A^T) of an NCHW tensor [N,3,S,S] -> [N,3,S,S]; float64.  (`stride` is ignored: nothing decimates.)"""
+        S = self.in_shape[-1]
+        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
+        N = x64.shape[0]
+        assert tuple(x64.shape[1:]) == (3, S, S), f"varying_blur: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
+        out = torch.empty(N, 3, S, S, dtype=F64, device=self.device)
+        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)  # (fh_conv_blend checks the planes it holds)
+        return ctx.blur_blend(x64, out, self.frame_taps, self.blend, 3 * N, adjoint)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # ONE noise draw at the image's shape
+        y = self._noise(self._conv(data).to(data.dtype), noiseless)
+        self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.in_shape[-3:])
+        return self._conv(y, adjoint=True).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`, for DPS"""
+        return self._conv(v, adjoint=True).to(v.dtype)
+
+    def folded_bases(self):
+        return None
+
+    def folded_sr_bases(self):
+        return None
+
+
 def poisson_gaussian_sigma(y, gain, read_sigma):
     """Plug-in noise map of a Poisson-Gaussian sensor, sigma = 2 sqrt(gain clip((y + 1) / 2, 0, 1) + read_sigma^2): `y` in the
     [-1, 1] units of the measurements (array or tensor), `gain` and `read_sigma` in intensity units of [0, 1]; the factor 2 maps

@@ -113,6 +113,7 @@ def main(argv=None):
                          scale_factor=o.scale_factor, in_shape=(1, 3, S, S), kernel_path=o.kernel_path or None,
                          mask_path=o.mask_path or None, mask_border=o.mask_border, frame_shifts=o.frame_shifts or None,
                          frame_sigmas=o.frame_sigmas or None, mosaic=o.mosaic or None,
+                         blend_path=o.blend_path or None, psf_grid=o.psf_grid or None,
                          mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
                                    "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
                                    if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})

@@ -234,6 +234,40 @@ int fh_conv_frames(fh_context* ctx, const double* in, double* out, const int32_t
                    void* stream);
 int fh_conv_frames_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int stride, int adjoint, int32_t out[6]);
 
+/* Spatially varying blur (fh_problem.op = 14): the Nagy-O'Leary interpolation of nframes = K shift-invariant blurs,
+ *   A = sum_k diag(U_k) B_k,   A^T = sum_k B_k^T diag(U_k),
+ * B_k the stride-1 circular convolution of fh_conv_circ with tap list k, U_k a per-pixel blend map (normally a partition of
+ * unity; any finite maps give a linear A).  dy / dx / w, frame_off, max_frame_taps and halo as for fh_conv_frames (lists
+ * concatenated in PSF order, frame_off a DEVICE int32 [K + 1], halo = 1000 + 64 hy + hx over ALL PSFs), 1 <= K <= 16;
+ * blend is float64 [K][3][S][S], shared by all images: plane p reads the map of PSF k at blend + (3 k + p % 3) S S.
+ * in, out [planes][S][S], planes = 3 * nimg (nimg <= FH_MAX_BATCH):
+ *   adjoint = 0:  out[p] = sum_k blend[k][p % 3] .* conv(in[p]; list k)
+ *   adjoint = 1:  out[p] = sum_k conv^T(blend[k][p % 3] .* in[p]; list k)
+ * Arithmetic: every convolution is one fma chain from 0 in list order.  Forward, t_k is multiplied by its map (the product
+ * rounded) and the frames are accumulated in index order, acc = U_0 t_0, then acc = fma(1, acc, U_k t_k) - k_mask's
+ * expression.  Adjoint, the product U_k .* in is rounded, and the frames' sums are added in index order, one rounding each.
+ * The result therefore does not depend on the route (blend_plan, csrc/fh_kernels.hip; fh_conv_blend_plan reports the
+ * decision without a context or a device, out = {route: 1 fused - it has a launch for every legal argument and is the default -
+ * grid x, grid y, grid z, block size, dynamic LDS bytes}, zeros on an error):
+ *   fused: ONE launch of k_conv_blend - forward, the input tile is staged once for the union of the extents and the PSFs take
+ *          turns in the tap staging; adjoint, the tile of U_k .* in is re-staged per PSF.  A 32 x 64 output tile where its
+ *          LDS fits 64 KiB, else a 32 x 16 tile (76 KiB at extents 32 with 1024 taps); edge guards, so any even S tiles;
+ *   chain: per PSF fh_conv_circ's launch and one streaming multiply through a work vector of the context.
+ *          FH_BLEND_FUSED=0 forces it (A/B switch, read at every call) wherever its kernels fit their 64 KiB (at wide extents
+ *          with several hundred taps they do not, and the fused kernel runs whatever the switch says).
+ * The call reads frame_off back (one stream synchronisation) and checks it.  FH_EINVAL before any launch: a null pointer,
+ * in == out, S odd or outside 2 .. 256, K outside 1 .. 16, max_frame_taps outside 1 .. 1024, halo not a 2-D code with
+ * extents <= 32, planes < 3, not a multiple of 3 or beyond 3 FH_MAX_BATCH, adjoint outside 0 / 1, offsets that are not
+ * increasing from 0 or hold a list longer than max_frame_taps; FH_ESIZE: planes beyond the context's (or 65535) - the only
+ * size refusal: the 32 x 16 tile fits the opt-in at every legal extent and tap count.
+ * Work vector: on the chain route the call writes one of the context's work vectors, the ones fh_amm and fh_cg_solve[_batched]
+ * use.  Like those entry points it therefore must not run concurrently, from another stream or host thread, with any other call
+ * on the SAME context; give concurrent users their own contexts. */
+int fh_conv_blend(fh_context* ctx, const double* in, double* out, const int32_t* dy, const int32_t* dx, const double* w,
+                  const int32_t* frame_off, int nframes, int max_frame_taps, int halo, const double* blend, int planes,
+                  int adjoint, void* stream);
+int fh_conv_blend_plan(int S, int nframes, int max_frame_taps, int halo, int planes, int adjoint, int32_t out[6]);
+
 /* Circular 2-D convolution with a DENSE window win[2 hy + 1][2 hx + 1] (row-major, centre at (hy, hx), 0 <= hy, hx <= 32; zeros
  * inside the window are allowed) over in[planes][S][S] at stride 1 - fh_conv_circ's definition with dy = a, dx = b and no
  * limit on the number of non-zeros (a measured PSF, a defocus disk, a rotated Gaussian):
@@ -311,6 +345,17 @@ typedef struct fh_problem {
    * weights with sigma_y2 = s^2 give the bits of op 12, K = 1 those of op 10.  FH_FRAMES_FUSED is read as for op 12.  mask == NULL
    * or a null per->mask[i]: FH_EINVAL before any launch and before the offsets are read.  The first such solve of a context
    * allocates one more CG vector (W p), as for ops 8 .. 11.
+   * 14 spatially varying blur: y = sum_k U_k .* (B_k x) + n, A the operator pair of fh_conv_blend.  stride = 1; tap_dy / tap_dx /
+   * tap_w the tap lists of all K PSFs concatenated and ntaps their total; ntaps2 = K, 1 <= K <= 16; tap2_dy a DEVICE int32 [K + 1]
+   * of offsets into the lists; halo2 the largest tap count of one PSF, 1 .. 1024 (K <= ntaps <= K halo2); halo = 1000 + 64 hy + hx
+   * with the extents (<= 32) over ALL PSFs; tap2_w the blend maps, float64 [K][3][S][S], shared by every image of a batch.
+   * tap2_dx, the four fold_* and mask (per->mask[i]) null, fold_sym = 0; use_dct 0 or 1.  The measurement - u, b, x - keeps the
+   * image's size, [3][S][S] per image.  A_mm(u) = sigma_y2 u + A C A^T u; the forward blend finishes with the sigma_y2 u term,
+   * frame 0 as fma(sigma_y2, u, U_0 t_0).  A solve (and fh_amm) reads the offsets back and checks them once, before its launches.
+   * Anything else: FH_EINVAL before any launch.  No p.Ap partials come out of the operator: the CG runs its dot kernel, as for
+   * ops 2 and 12.  FH_BLEND_FUSED is read as by fh_conv_blend, and the CG graph cache keys on it and on the offsets.  K = 1 with
+   * an all-ones map gives the bits of op 1 on its plain tap list; one-hot maps over identical PSFs give, in the FORWARD direction,
+   * those of one fh_conv_circ (the adjoint adds K separately rounded pieces and agrees to rounding only).
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
