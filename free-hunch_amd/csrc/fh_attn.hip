@@ -245,11 +245,15 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(AttnArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // backward, key side: dV = P^T dO, dK = scale * dZ^T Q (P, dZ recomputed per 32-query tile)
+// The Q tile is staged times scale * log2(e), the factor the forward kernel and k_attn_bwd_dq put on their query registers:
+// the recomputed logits are then the forward's bit for bit (same products, same contraction order), and P = exp2(S - lse) is
+// consistent with the stored log-sum-exp.  Scaling the finished dot product instead rounds differently, by some ulps OF THE
+// LOGIT: at |S| ~ 100 that is a relative error of 1e-5 in P, which a saturated row (P ~ 1) passes straight on to dV.
 // ------------------------------------------------------------------------------------------------
 template <int D>
 __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
   constexpr int DH = D / 2, DT = D / 32, KLD = D + 4, C4 = D / 4;
-  __shared__ __align__(16) float Qs[2][32][KLD];
+  __shared__ __align__(16) float Qs[2][32][KLD];  // Q tile times scale * log2(e)
   __shared__ __align__(16) float Os[2][32][KLD];  // dO tile
   __shared__ __align__(16) float Ls[2][2][32];    // [buf][0: lse, 1: rowsum(dO . O)][query]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
@@ -266,6 +270,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
   }
   f4 rq[DT], ro[DT];
   float rl = 0.f;
+  const float sl2 = a.scale * kLog2e;
   auto load_tile = [&](int qt) {
 #pragma unroll
     for (int e = 0; e < DT; ++e) {
@@ -279,7 +284,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
 #pragma unroll
     for (int e = 0; e < DT; ++e) {
       const int idx = e * 256 + tid, q = idx / C4, c4 = idx % C4;
-      *reinterpret_cast<f4*>(&Qs[buf][q][4 * c4]) = rq[e];
+      *reinterpret_cast<f4*>(&Qs[buf][q][4 * c4]) = rq[e] * sl2;
       *reinterpret_cast<f4*>(&Os[buf][q][4 * c4]) = ro[e];
     }
     if (tid < 64) Ls[buf][tid >> 5][tid & 31] = rl;
@@ -289,7 +294,6 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) dk[dt][r] = dv[dt][r] = 0.f;
-  const float sl2 = a.scale * kLog2e;
   const int nqt = a.T / 32;
   load_tile(0);
   store_tile(0);
@@ -298,7 +302,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
     const int buf = qt & 1;
     if (qt + 1 < nqt) load_tile(qt + 1);
     if (active) {
-      floatx16 s = rows_times_regs<DH, KLD>(Qs[buf], lr, lh, kreg);   // S tile: rows = queries, column = this lane's key
+      floatx16 s = rows_times_regs<DH, KLD>(Qs[buf], lr, lh, kreg);   // S tile (log2 units): rows = queries, column = this lane's key
       floatx16 dp = rows_times_regs<DH, KLD>(Os[buf], lr, lh, vreg);  // dP tile
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -307,20 +311,20 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(AttnArgs a) {
         const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq_[4] = {d4.x, d4.y, d4.z, d4.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          const float p = ex2(s[4 * j + i] * sl2 - lq[i]);
+          const float p = ex2(s[4 * j + i] - lq[i]);
           s[4 * j + i] = p;
           dp[4 * j + i] = p * (dp[4 * j + i] - dq_[i]);
         }
       }
       cols_times_acc<DT, KLD>(Os[buf], lr, lh, s, dv);   // dV^T += dO^T P
-      cols_times_acc<DT, KLD>(Qs[buf], lr, lh, dp, dk);  // dK^T += Q^T dZ
+      cols_times_acc<DT, KLD>(Qs[buf], lr, lh, dp, dk);  // dK^T += (scale log2(e) Q)^T dZ
     }
     if (qt + 1 < nqt) store_tile(buf ^ 1);
     __syncthreads();
   }
   if (active) {
     float* rowp = a.dqkv + ((int64_t)n * a.T + k0 + lr) * row + h * a.hs;
-    store_cols<DT>(dk, a.scale, rowp + a.ko, lh);
+    store_cols<DT>(dk, a.scale / sl2, rowp + a.ko, lh);  // (the staging factor taken out again)
     store_cols<DT>(dv, 1.f, rowp + a.vo, lh);
   }
 }

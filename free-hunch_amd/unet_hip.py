@@ -491,50 +491,41 @@ class HipOps:
             hs, qo, ko, vo = 3 * ch, 0, ch, 2 * ch
         return ch, hs, qo, ko, vo
 
-    def _attn_fwd(self, p, x, heads, tape):
-        N, H, W, C = x.shape
-        T = H * W
-        hn, st = self._gn(p + ".norm", x, act=0)
-        qkv = self._conv(p + ".qkv", hn)  # [N,H,W,3C]
+    def _attn_core_fwd(self, qkv, N, T, C, heads):
+        """softmax(q k^T / sqrt(ch)) v of qkv [N][T][3C] per (image, head) -> (A [N][T][C], saved): the fused kernel where it
+        supports the shape (saved = (A, log-sum-exp)), else three kernels with the weights materialised (saved = S)."""
         if (_switch("ATTN_FUSED") and self.lib.fh_attention_supported(T, C, heads)
                 and N * heads <= 65535):  # (image, head) pairs ride in gridDim.y
             # one kernel: q k^T -> online softmax -> . v; the tape keeps the output and the log-sum-exp, not the weights
-            A = torch.empty(N, H, W, C, dtype=torch.float32, device=x.device)
-            lse = torch.empty(N * heads, T, dtype=torch.float32, device=x.device)
+            A = torch.empty(N, T, C, dtype=torch.float32, device=qkv.device)
+            lse = torch.empty(N * heads, T, dtype=torch.float32, device=qkv.device)
             _lib.check(self.lib.fh_attention_fwd(qkv.data_ptr(), A.data_ptr(), lse.data_ptr(), N, T, C, heads,
                                                  int(self.cfg.use_new_attention_order), _lib.stream()), "attention_fwd")
-            out = self._conv(p + ".proj_out", A, res=x)
-            tape.append(("attn", p, x, st, qkv, (A, lse), heads))
-            return out
+            return A, (A, lse)
         ch, hs, qo, ko, vo = self._attn_geometry(N, T, C, heads)
-        S = torch.empty(N * heads, T, T, dtype=torch.float32, device=x.device)
+        S = torch.empty(N * heads, T, T, dtype=torch.float32, device=qkv.device)
         base, fs = qkv.data_ptr(), 4
         s3 = (T * 3 * C, hs)
         self._bgemm(base + qo * fs, base + ko * fs, S.data_ptr(), T, T, ch, 3 * C, 3 * C, T, 0, 0, N * heads, heads,
                     s3, s3, (heads * T * T, T * T), alpha=1.0 / math.sqrt(ch))
         _lib.check(self.lib.fh_softmax_rows(S.data_ptr(), N * heads * T, T, _lib.stream()), "softmax")
-        A = torch.empty(N, H, W, C, dtype=torch.float32, device=x.device)
+        A = torch.empty(N, T, C, dtype=torch.float32, device=qkv.device)
         self._bgemm(S.data_ptr(), base + vo * fs, A.data_ptr(), T, ch, T, T, 3 * C, C, 0, 1, N * heads, heads,
                     (heads * T * T, T * T), s3, (T * C, ch))
-        out = self._conv(p + ".proj_out", A, res=x)
-        tape.append(("attn", p, x, st, qkv, S, heads))
-        return out
+        return A, S
 
-    def _attn_bwd(self, rec, g, add2=None):
-        _, p, x, st, qkv, S, heads = rec
-        N, H, W, C = x.shape
-        T = H * W
+    def _attn_core_bwd(self, qkv, saved, gA, N, T, C, heads):
+        """dL/dqkv [N][T][3C] of `_attn_core_fwd` given gA = dL/dA and what the forward saved"""
         ch, hs, qo, ko, vo = self._attn_geometry(N, T, C, heads)
-        gA = self._dgrad(p + ".proj_out", g)  # [N,H,W,C]
         dqkv = torch.empty_like(qkv)
-        if isinstance(S, tuple):  # fused form: the weights are recomputed from q, k and the log-sum-exp
-            A, lse = S
+        if isinstance(saved, tuple):  # fused form: the weights are recomputed from q, k and the log-sum-exp
+            A, lse = saved
             dsum = torch.empty_like(lse)
             _lib.check(self.lib.fh_attention_bwd(qkv.data_ptr(), A.data_ptr(), gA.data_ptr(), lse.data_ptr(), dsum.data_ptr(),
                                                  dqkv.data_ptr(), N, T, C, heads, int(self.cfg.use_new_attention_order),
                                                  _lib.stream()), "attention_bwd")
-            g_hn = self._dgrad(p + ".qkv", dqkv, gn=(p + ".norm", x, st, 0, None, None))
-            return self._gn_bwd(p + ".norm", x, st, g_hn, 0, accumulate_into=g, add2=add2)
+            return dqkv
+        S = saved
         base, dbase, fs = qkv.data_ptr(), dqkv.data_ptr(), 4
         s3, sS, sA = (T * 3 * C, hs), (heads * T * T, T * T), (T * C, ch)
         B_ = N * heads
@@ -550,6 +541,22 @@ class HipOps:
                     alpha)
         self._bgemm(dP.data_ptr(), base + qo * fs, dbase + ko * fs, T, ch, T, T, 3 * C, 3 * C, 1, 1, B_, heads, sS, s3, s3,
                     alpha)
+        return dqkv
+
+    def _attn_fwd(self, p, x, heads, tape):
+        N, H, W, C = x.shape
+        hn, st = self._gn(p + ".norm", x, act=0)
+        qkv = self._conv(p + ".qkv", hn)  # [N,H,W,3C]
+        A, saved = self._attn_core_fwd(qkv, N, H * W, C, heads)
+        out = self._conv(p + ".proj_out", A.view(N, H, W, C), res=x)
+        tape.append(("attn", p, x, st, qkv, saved, heads))
+        return out
+
+    def _attn_bwd(self, rec, g, add2=None):
+        _, p, x, st, qkv, saved, heads = rec
+        N, H, W, C = x.shape
+        gA = self._dgrad(p + ".proj_out", g)  # [N,H,W,C]
+        dqkv = self._attn_core_bwd(qkv, saved, gA, N, H * W, C, heads)
         g_hn = self._dgrad(p + ".qkv", dqkv, gn=(p + ".norm", x, st, 0, None, None))
         return self._gn_bwd(p + ".norm", x, st, g_hn, 0, accumulate_into=g, add2=add2)
 

@@ -893,8 +893,10 @@ def _attention_float64(qkv, heads, new_order):
                                    (1, 1024, 256, 4, 0), (2, 32, 64, 1, 0)])
 def test_fused_attention_vs_float64(dev, shape):
     """One-kernel attention and its recomputing backward against the reference's two attention orders in float64: output,
-    dq / dk / dv within fp32 rounding (5e-6 of scale; the three-kernel path with materialised weights is held to the same),
-    and the two paths agree with each other to that order.  T = 96 (not a multiple of 128) exercises idle waves."""
+    dq / dk / dv within fp32 rounding (5e-6 of scale).  T = 96 (not a multiple of 128) exercises idle waves.  The three-kernel
+    path with materialised weights is held to the same bound by test_three_kernel_attention_vs_float64, the agreement of the
+    two paths by test_fused_and_three_kernel_attention_agree, and logits of +-60 nats and more by
+    test_fused_attention_at_hard_softmax_inputs (all in tests/test_attention_paths_gpu.py)."""
     L, lib = _lib()
     N, T, C, heads, new_order = shape
     assert lib.fh_attention_supported(T, C, heads) == 1
