@@ -59,6 +59,9 @@ _SIGS = {
     "fh_dct_sym_plan": ([C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4 + [C.POINTER(C.c_int64)], C.c_int),
     "fh_dct_rect": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int),
     "fh_dct_rect_plan": ([C.c_int] * 4 + [C.POINTER(C.c_int32)], C.c_int),
+    "fh_hartley_fix": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_double, C.c_int, C.c_void_p], C.c_int),
+    "fh_hartley2d": ([C.c_void_p, c_dp, c_dp, c_dp, C.c_int, C.c_void_p], C.c_int),
+    "fh_hartley2d_plan": ([C.c_int, C.c_int, C.POINTER(C.c_int32)], C.c_int),
     "fh_dct_moments_u8": ([C.c_void_p, c_dp, C.c_int, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_rep_apply": ([C.c_void_p, c_dp, c_dp, c_dp, c_dp, C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
     "fh_rep_apply_batched": ([C.c_void_p, C.POINTER(FhBatch), C.c_int, c_dp, c_dp, C.c_int64, C.c_int, C.c_void_p], C.c_int),
@@ -241,6 +244,15 @@ class Context:
         assert x.numel() == planes * a * a and out.numel() == planes * b * b and P_w.numel() == P_h.numel() == self.S * So
         check(self.lib.fh_dct_rect(self.h, ptr(x), ptr(out), ptr(P_w), ptr(P_h), So, planes, int(inverse), stream()),
               "fh_dct_rect")
+        return out
+
+    def hartley2d(self, x, out, Hc):
+        """out = H x per plane (fh_hartley2d), the orthonormal 2-D discrete Hartley transform; Hc the [S][S] float64 basis of
+        `measurements.folded_dct_hartley_bases`.  Self-inverse; x may be out."""
+        planes = x.numel() // (self.S * self.S)
+        assert x.dtype == out.dtype == Hc.dtype == torch.float64
+        assert x.numel() == out.numel() == planes * self.S * self.S and Hc.numel() == self.S * self.S
+        check(self.lib.fh_hartley2d(self.h, ptr(x), ptr(out), ptr(Hc), planes, stream()), "fh_hartley2d")
         return out
 
     def dct_moments_u8(self, imgs, work, sum_, sumsq):

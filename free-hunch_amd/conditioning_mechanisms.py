@@ -66,10 +66,14 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
 # (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
 # into rectangular DCT bases op = 7, see _problem; a weighted_blur on the dense-window kernel is op = 9, a weighted_sr on the
 # rectangular bases op = 11; burst_sr is op = 12, the multi-frame operator pair of fh_conv_frames, and weighted_burst_sr is
-# op = 13, the same pair with a noise map on the burst; varying_blur is op = 14, the blended PSFs of fh_conv_blend)
+# op = 13, the same pair with a noise map on the burst; varying_blur is op = 14, the blended PSFs of fh_conv_blend;
+# fourier_sampling, op = 15, lives in _OP_CODE_MORE below: look names up with _op_code)
 _OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
             "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10,
             "burst_sr": 12, "weighted_burst_sr": 13, "varying_blur": 14}
+# operators added after the table above was pinned by the tests; fourier_sampling is op = 15, measurement in the Hartley domain
+# (fh_hartley2d) with the sampling mask or the 1 / sigma map as the solver's weights
+_OP_CODE_MORE = {"fourier_sampling": 15}
 _MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
 # operators whose PSF is the caller's: a lock-step batch must share it
 _SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr")
@@ -79,9 +83,22 @@ _DECIMATING = ("super_resolution", "custom_sr", "weighted_sr", "burst_sr", "weig
 _WEIGHTED = ("weighted_blur", "weighted_sr", "weighted_burst_sr")
 # operators on K frames with one PSF each: A is the operator pair of fh_conv_frames, the measurement [3 K, So, So] per image
 _BURST = ("burst_sr", "weighted_burst_sr")
+# Fourier-domain measurement: whitened like _WEIGHTED through operator.weights, which is the 0/1 mask (sigma_y2 from sigma_s)
+# or 1 / sigma of a noise map (sigma_y2 = 1)
+_FOURIER = ("fourier_sampling",)
 _BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
                  "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'. Also 'burst_sr' and "
-                 "'weighted_burst_sr'. Also 'varying_blur'.")
+                 "'weighted_burst_sr'. Also 'fourier_sampling'. Also 'varying_blur'.")
+
+
+def _op_code(name):
+    """fh_problem.op of an operator name, None for a name the solver does not know"""
+    return _OP_CODE.get(name, _OP_CODE_MORE.get(name))
+
+
+def _whitened(name):
+    """the solver multiplies operator.weights into the right-hand side and into the solution (W (y - A0 x0), A0^T W u)"""
+    return name in _WEIGHTED or name in _FOURIER
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -94,7 +111,7 @@ def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
 
 def _problem(operator, cov, sigma_y2):
     p = _lib.FhProblem()
-    p.op = _OP_CODE[operator.name]
+    p.op = _op_code(operator.name)
     p.use_dct = int(cov.use_dct)
     p.planes = 3
     p.stride = int(operator.scale_factor) if operator.name in _DECIMATING else 1
@@ -127,6 +144,13 @@ def _problem(operator, cov, sigma_y2):
         p.tap_dy, p.tap_dx, p.tap_w = ft.dy.data_ptr(), ft.dx.data_ptr(), ft.w.data_ptr()
         p.ntaps2, p.halo2, p.tap2_dy, p.tap2_w = ft.nframes, ft.max_taps, ft.off.data_ptr(), blend.data_ptr()
         keep.extend([ft.dy, ft.dx, ft.w, ft.off, blend])
+        return p, keep
+    if operator.name in _FOURIER:  # op 15: P = C_dct Hc (or Hc) on both sides, no taps; the weights kept LAST in `keep`
+        P, Pt = operator.folded_hartley_bases(cov.use_dct, cov.device)
+        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
+        p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = P.data_ptr(), P.data_ptr(), Pt.data_ptr(), Pt.data_ptr()
+        p.mask = w.data_ptr()
+        keep.extend([P, Pt, w])
         return p, keep
     if operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
         w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
@@ -169,6 +193,8 @@ def _problem(operator, cov, sigma_y2):
 def _solver_sigma_y2(operator):
     """sigma_y2 of the system the device solves: `_sigma_y2`, or 1 for the whitened system of a noise-map operator (its
     `sigma_s` is not read)"""
+    if operator.name in _FOURIER:  # the mask alone: the scalar level under the blur rule; a noise map: the whitened system
+        return 1.0 if operator.noise_map is not None else _sigma_y2(operator)
     return 1.0 if operator.name in _WEIGHTED else _sigma_y2(operator)
 
 
@@ -190,7 +216,7 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     ctx = cov.ctx
     dev = cov.device
     name = operator.name
-    if name not in _OP_CODE:
+    if _op_code(name) is None:
         raise ValueError(_BAD_OPERATOR)
     prob, keep = _problem(operator, cov, _solver_sigma_y2(operator))
     prob.cg_scipy = int(bool(scipy_cg))
@@ -206,7 +232,7 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     else:
         ax = operator._conv(x64, stride=prob.stride)
         b = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur" or name in _WEIGHTED:  # b = M (y - B x0); noise map: the whitened b = W (y - A0 x0)
+        if name == "masked_blur" or _whitened(name):  # b = M (y - B x0); noise map: the whitened b = W (y - A0 x0)
             b = (keep[-1].view_as(b) * b).contiguous()
     sol = torch.empty_like(b)
     info = _lib.FhCgInfo()
@@ -225,7 +251,7 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
         return sol
     if name == "colorization":
         return operator._mix(sol, adjoint=True)
-    if name in _WEIGHTED:  # mat = A0^T W u
+    if _whitened(name):  # mat = A0^T W u
         sol = (keep[-1].view_as(sol) * sol).contiguous()
     return operator._conv(sol, stride=prob.stride, adjoint=True)
 
@@ -241,7 +267,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     B = len(operators)
     op0, cov0 = operators[0], covariance_models[0]
     name = op0.name
-    if name not in _OP_CODE:
+    if _op_code(name) is None:
         raise ValueError(_BAD_OPERATOR)
     dev, S = cov0.device, cov0.S
     # scratch sized for the whole batch; one context per lock-step GROUP (keyed by the group's first image slot), so
@@ -280,7 +306,11 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             mk = op.mask.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
             per.mask[b] = mk.data_ptr()
-        if name in _WEIGHTED:  # every image brings its own noise map
+        if name in _FOURIER:
+            assert op.in_shape[-1] == S and op0.in_shape[-1] == S, "lock-step images must share the image side"
+            assert (op.noise_map is None) == (op0.noise_map is None) and _solver_sigma_y2(op) == prob.sigma_y2, \
+                "lock-step images must all carry a noise map or share the noise level"
+        if _whitened(name):  # every image brings its own noise map (fourier_sampling: its own sampling mask)
             mk = op.weights.to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
             per.mask[b] = mk.data_ptr()
@@ -295,6 +325,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
             out = torch.empty(B, 3 if adjoint else 3 * op0.nframes, so, so, dtype=F64, device=dev)
             return ctx.blur_frames(v, out, op0.frame_taps, planes, prob.stride, adjoint)
         out = torch.empty(B, 3, so, so, dtype=F64, device=dev)
+        if name in _FOURIER:  # the Hartley transform, its own adjoint
+            return ctx.hartley2d(v, out, op0.folded_hartley_bases(False, dev)[0])
         if name == "varying_blur":  # the blended PSFs, the maps shared by the images
             return ctx.blur_blend(v, out, op0.frame_taps, blend, planes, adjoint)
         return ctx.blur(v, out, op0.taps, planes, prob.stride, adjoint)
@@ -313,7 +345,7 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     else:
         ax = conv(x64, False)
         b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur" or name in _WEIGHTED:  # b = M (y - B x0) / W (y - A0 x0), each image with its own map
+        if name == "masked_blur" or _whitened(name):  # b = M (y - B x0) / W (y - A0 x0), each image with its own map
             b_vec = (torch.cat([k.view(1, *b_vec.shape[1:]) for k in keep[-B:]], 0) * b_vec).contiguous()
     sol = torch.empty_like(b_vec)
     rtol = rtol_func(sigma_t, max_rtol)
@@ -329,14 +361,14 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
                               "residual_norm": infos[b].residual_norm, "rtol": rtol})
     if name in _MASKED:
         return sol
-    if name in _WEIGHTED:  # mat = A0^T W u
+    if _whitened(name):  # mat = A0^T W u
         sol = (torch.cat([k.view(1, *sol.shape[1:]) for k in keep[-B:]], 0) * sol).contiguous()
     return mix(sol, True) if name == "colorization" else conv(sol, True)
 
 
 def choose_solver(operator_name, operator, y, x0_mean, theta0_var=None, covariance_model=None, method="customcuda",
                   max_rtol=1, ortho_tf=None, sigma_t=None, use_rtol_func=False, info_out=None):
-    if operator_name not in _OP_CODE:
+    if _op_code(operator_name) is None:
         raise ValueError(_BAD_OPERATOR)
     if method == "customcuda":
         return solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, info_out)

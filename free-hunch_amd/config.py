@@ -71,6 +71,12 @@ SCHEMA = {
     # (K <= 16) and exactly one of --blend_path (a .npy of blend maps [K,S,S], [K,3,S,S] or [3K,S,S]) and --psf_grid=RxC (the
     # PSFs on an R x C grid, R * C = K, blended bilinearly between the cell centres: measurements.grid_blend_weights)
     "blend_path": (str, ""), "psf_grid": (str, ""),
+    # NEW: --operator_name=fourier_sampling, undersampled k-space measured in the Hartley domain: the sampling mask is either
+    # --mask_path (a 0/1 .npy [S,S], [3,S,S] or [1,3,S,S] in FFT order, DC at [0,0]; OR-ed with its point reflection) or
+    # --kspace_pattern=cartesian|radial with --kspace_acceleration=R (and --kspace_center_fraction, --kspace_seed:
+    # measurements.kspace_mask); --noise_map_path optionally gives the noise level per frequency (inf = not measured)
+    "kspace_pattern": (str, ""), "kspace_acceleration": (float, None), "kspace_center_fraction": (float, None),
+    "kspace_seed": (int, None),
 }
 
 
@@ -118,6 +124,27 @@ def load_config(argv=None):
     elif cfg["blend_path"] or cfg["psf_grid"]:
         raise SystemExit(f"--blend_path and --psf_grid belong to --operator_name=varying_blur; operator "
                          f"'{cfg['operator_name']}' does not read them")
+    kspace = [k for k in ("kspace_pattern", "kspace_acceleration", "kspace_center_fraction", "kspace_seed")
+              if cfg[k] not in ("", None)]
+    if cfg["operator_name"] == "fourier_sampling":
+        if bool(cfg["mask_path"]) == bool(cfg["kspace_pattern"]):
+            raise SystemExit("--operator_name=fourier_sampling needs its sampling mask: exactly one of --mask_path=FILE.npy and "
+                             "--kspace_pattern=cartesian|radial (with --kspace_acceleration=R)")
+        if cfg["kspace_pattern"] and cfg["kspace_pattern"] not in ("cartesian", "radial"):
+            raise SystemExit(f"--kspace_pattern is cartesian or radial, got '{cfg['kspace_pattern']}'")
+        if cfg["kspace_pattern"] and cfg["kspace_acceleration"] is None:
+            raise SystemExit("--kspace_pattern needs --kspace_acceleration=R (R >= 1: the undersampling factor)")
+        if cfg["mask_path"] and kspace:
+            raise SystemExit("--kspace_acceleration, --kspace_center_fraction and --kspace_seed go with --kspace_pattern, not with "
+                             "--mask_path")
+        if cfg["mask_border"] != 0:
+            raise SystemExit("--mask_border belongs to --operator_name=masked_blur; operator 'fourier_sampling' does not read it")
+        if cfg["noise_gain"] is not None or cfg["noise_read_sigma"] is not None:
+            raise SystemExit("--noise_gain and --noise_read_sigma belong to --operator_name=weighted_blur / weighted_sr / "
+                             "weighted_burst_sr; operator 'fourier_sampling' reads --noise_map_path only")
+    elif kspace:
+        raise SystemExit(f"--kspace_pattern, --kspace_acceleration, --kspace_center_fraction and --kspace_seed belong to "
+                         f"--operator_name=fourier_sampling; operator '{cfg['operator_name']}' does not read them")
     if cfg["frame_shifts"] and cfg["operator_name"] not in ("burst_sr", "weighted_burst_sr"):
         raise SystemExit(f"--frame_shifts belongs to --operator_name=burst_sr (and weighted_burst_sr); operator "
                          f"'{cfg['operator_name']}' does not read it")
@@ -140,12 +167,13 @@ def load_config(argv=None):
         if bool(cfg["noise_map_path"]) == sensor:
             raise SystemExit(f"--operator_name={cfg['operator_name']} needs a noise map: either --noise_map_path=FILE.npy or "
                              "--noise_gain=G --noise_read_sigma=R, not both")
-    elif cfg["noise_map_path"] or sensor:
+    elif (cfg["noise_map_path"] or sensor) and cfg["operator_name"] != "fourier_sampling":
         raise SystemExit(f"--noise_map_path, --noise_gain and --noise_read_sigma belong to --operator_name=weighted_blur / "
-                         f"weighted_sr / weighted_burst_sr; operator '{cfg['operator_name']}' does not read them")
-    if cfg["operator_name"] != "masked_blur" and (cfg["mask_path"] or cfg["mask_border"] != 0):
-        raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur; operator "
+                         f"weighted_sr / weighted_burst_sr (--noise_map_path also to fourier_sampling); operator "
                          f"'{cfg['operator_name']}' does not read them")
+    if cfg["operator_name"] not in ("masked_blur", "fourier_sampling") and (cfg["mask_path"] or cfg["mask_border"] != 0):
+        raise SystemExit(f"--mask_path and --mask_border belong to --operator_name=masked_blur (--mask_path also to "
+                         f"fourier_sampling); operator '{cfg['operator_name']}' does not read them")
     if cfg["kernel_path"] and cfg["operator_name"] not in ("custom_blur", "masked_blur", "custom_sr", "weighted_blur",
                                                            "weighted_sr", "burst_sr", "weighted_burst_sr", "varying_blur"):
         raise SystemExit(f"--kernel_path is the PSF of --operator_name=custom_blur / masked_blur / custom_sr / weighted_blur / "

@@ -1389,6 +1389,123 @@ __global__ __launch_bounds__(256) void k_mask(fh_batch per, const double* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Hartley butterfly (fh_hartley_fix, fh_hartley2d, fh_problem.op = 15).  With Hc[u][n] = (cos + sin)(2 pi u n / S) / sqrt(S) the
+// separable transform T = Hc X Hc is NOT the 2-D discrete Hartley transform H X = Re F X - Im F X; the butterfly
+//   R(T)[u][v] = 1/2 ((T[u][v] + T[-u][v]) + (T[u][-v] - T[-u][-v])),        -u = (S - u) % S
+// turns one into the other (cas(a + b) = 1/2 (cas a cas b + cas(-a) cas b + cas a cas(-b) - cas(-a) cas(-b))), and R R = I.
+// A work unit is a row pair (u, -u), u = 0 .. S/2 (rows 0 and S/2 are their own reflections): the workgroup stages both rows
+// (times the input weights, the product rounded) in LDS with 16-byte loads, then every thread forms a 16-byte pair of outputs
+// of either row, reading the two staged rows at the mirrored columns in reverse.  Block x of the grid owns units x, x + gridDim.x,
+// ... of every plane it visits, grid y walks the planes (p, p + gridDim.y, ...): which elements a block sums for the p.Ap
+// partial of (image, channel, block x), and in what order, depends on S alone - a batched solve repeats the single one.
+//   value = 1/2 ((a + b) + (c - d)) in that order;  with output weights w * value (rounded);  with add fma(add_scale, add, .)
+// Weights: plane p reads table[image] + (p % 3) S S (`wshared`: table[0] for every image, the entry point's one map).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_hartley_fix(const double* __restrict__ in, double* __restrict__ out, int S, int planes,
+                                                     fh_diag_tab win, fh_diag_tab wout, int wshared,
+                                                     const double* __restrict__ add, double add_scale,
+                                                     const fh_cg_state* __restrict__ states, double* __restrict__ dot_part,
+                                                     int dot_stride) {
+#pragma clang fp contract(off)  // the sums and the weight products are rounded one by one; fma() below stays an fma
+  extern __shared__ __align__(16) double hrows[];  // [2][S]: row u, row -u (weighted)
+  __shared__ double red[4];
+  const int tid = threadIdx.x, H = S / 2, units = H + 1;
+  const int64_t SS = (int64_t)S * S;
+  for (int p = (int)blockIdx.y; p < planes; p += (int)gridDim.y) {
+    const int img = p / 3, c = p % 3;
+    if (states != nullptr && states[img].done != 0) continue;  // (uniform over the workgroup)
+    const double* X = in + p * SS;
+    double* Y = out + p * SS;
+    const double* Wi = win.D[0] != nullptr ? win.D[wshared ? 0 : img] + c * SS : nullptr;
+    const double* Wo = wout.D[0] != nullptr ? wout.D[wshared ? 0 : img] + c * SS : nullptr;
+    const double* Ad = add != nullptr ? add + p * SS : nullptr;
+    double dsum = 0.0;
+    for (int u = (int)blockIdx.x; u < units; u += (int)gridDim.x) {
+      const int ur = (S - u) % S;
+      __syncthreads();  // the rows of the previous unit have been read
+      for (int i = tid; i < S; i += 256) {
+        const int r = i / H, j = i % H;
+        const int64_t o = (int64_t)(r ? ur : u) * S + 2 * j;
+        double2 v = *reinterpret_cast<const double2*>(X + o);
+        if (Wi != nullptr) {
+          const double2 w = *reinterpret_cast<const double2*>(Wi + o);
+          v = make_double2(w.x * v.x, w.y * v.y);
+        }
+        *reinterpret_cast<double2*>(hrows + r * S + 2 * j) = v;
+      }
+      __syncthreads();
+      for (int i = tid; i < S; i += 256) {
+        const int r = i / H, j = i % H;
+        if (r == 1 && ur == u) continue;  // a self-reflected row is written once
+        const double* A = hrows + r * S;        // this row
+        const double* B = hrows + (1 - r) * S;  // its reflection
+        const int v0 = 2 * j, v1 = v0 + 1, m0 = (S - v0) % S, m1 = S - v1;
+        double2 y = make_double2(0.5 * ((A[v0] + B[v0]) + (A[m0] - B[m0])), 0.5 * ((A[v1] + B[v1]) + (A[m1] - B[m1])));
+        const int64_t o = (int64_t)(r ? ur : u) * S + v0;
+        if (Wo != nullptr) {
+          const double2 w = *reinterpret_cast<const double2*>(Wo + o);
+          y = make_double2(w.x * y.x, w.y * y.y);
+        }
+        if (Ad != nullptr) {
+          const double2 a = *reinterpret_cast<const double2*>(Ad + o);
+          y = make_double2(fma(add_scale, a.x, y.x), fma(add_scale, a.y, y.y));
+          dsum = fma(a.x, y.x, dsum);
+          dsum = fma(a.y, y.y, dsum);
+        }
+        *reinterpret_cast<double2*>(Y + o) = y;
+      }
+    }
+    if (dot_part != nullptr) {  // (uniform) sum(add .* out) over this block's units of plane p
+      dsum = block_sum_256(dsum, red);
+      if (tid == 0) dot_part[(int64_t)img * dot_stride + c * (int)gridDim.x + (int)blockIdx.x] = dsum;
+    }
+  }
+}
+
+// Launch plan of the butterfly (host arithmetic only): S / 2 + 1 row pairs per plane over as few blocks x as walk them in the
+// same number of trips as 85 would (3 x 85 <= 256 partials per image; S = 256: 65 blocks of two pairs), and at most 48 planes -
+// the 3 FH_MAX_BATCH of a full batch - in grid y; more planes take further trips.  LDS: the two staged rows.
+struct hartley_plan_t {
+  int gx, gy;
+  int64_t lds_bytes;
+};
+static hartley_plan_t hartley_plan(int S, int planes) {
+  hartley_plan_t pn;
+  const int units = S / 2 + 1, trips = (units + 84) / 85;
+  pn.gx = (units + trips - 1) / trips;
+  pn.gy = planes < 3 * FH_MAX_BATCH ? planes : 3 * FH_MAX_BATCH;
+  pn.lds_bytes = (int64_t)2 * S * (int64_t)sizeof(double);
+  return pn;
+}
+
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// out = wout .* R(win .* in) (+ add_scale * add) over `planes` planes at the context's side; win / wout: per-image weight tables
+// (null: none), `wshared`: entry 0 serves every image.  in != out; every pointer 16-byte aligned (the callers check).
+static int hartley_launch(fh_context* ctx, const double* in, double* out, int planes, const fh_batch* win, const fh_batch* wout,
+                          int wshared, const double* add, double add_scale, const fh_cg_state* states, hipStream_t st,
+                          double* dot_part = nullptr, int dot_stride = 0, int* dot_nparts = nullptr) {
+  const int S = ctx->S;
+  if (dot_nparts != nullptr) *dot_nparts = 0;
+  if (planes < 1 || planes > 65535 || in == out) return FH_EINVAL;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  const hartley_plan_t pn = hartley_plan(S, planes);
+  fh_diag_tab ti, to;
+  memset(&ti, 0, sizeof(ti));
+  memset(&to, 0, sizeof(to));
+  for (int i = 0; win != nullptr && i < win->nimg && i < FH_MAX_BATCH; ++i) ti.D[i] = win->mask[i];
+  for (int i = 0; wout != nullptr && i < wout->nimg && i < FH_MAX_BATCH; ++i) to.D[i] = wout->mask[i];
+  if (add == nullptr) dot_part = nullptr;
+  if (dot_nparts != nullptr) *dot_nparts = dot_part != nullptr ? 3 * pn.gx : 0;
+  hipLaunchKernelGGL(k_hartley_fix, dim3(pn.gx, pn.gy), dim3(256), (size_t)pn.lds_bytes, st, in, out, S, planes, ti, to, wshared,
+                     add, add_scale, states, dot_part, dot_stride);
+  FH_LAUNCH_CHECK();
+  return 0;
+}
+
 // Channel mix of the colorization operator (grid z = image, one 16-byte pixel pair per thread, `pairs` = S*S/2 per plane):
 //   ADJ = 0:  out[img] = sum_c w[c] * in[img][c]  (+ add_scale * add[img])        in [nimg][3][S][S] -> out [nimg][S][S]
 //   ADJ = 1:  out[img][c] = w[c] * in[img]                                          in [nimg][S][S] -> out [nimg][3][S][S]
@@ -3119,7 +3236,14 @@ static int window_problem_check(const fh_problem* p) {
 // (the masks of a batched solve are per->mask[i]: masks_check)
 // S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 14) return FH_EINVAL;
+  if (p->op < 0 || p->op > 15) return FH_EINVAL;
+  if (p->op == 15) {  // Fourier sampling: the four [S][S] folded Hartley bases and the weights, nothing of the tap-list operators
+    if (p->stride != 1 || (p->use_dct != 0 && p->use_dct != 1) || p->fold_sym != 0 || p->mask == nullptr) return FH_EINVAL;
+    if (!p->fold_fwd_w || !p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
+    if (p->ntaps != 0 || p->ntaps2 != 0 || p->halo != 0 || p->halo2 != 0) return FH_EINVAL;
+    if (p->tap_dy || p->tap_dx || p->tap_w || p->tap2_dy || p->tap2_dx || p->tap2_w) return FH_EINVAL;
+    return 0;
+  }
   if (p->op == 14) {  // varying blur: ntaps2 = K PSFs, tap2_dy = their offsets, halo2 = the longest list, tap2_w = the blend maps
     const int K = p->ntaps2;
     conv_extent e;
@@ -3163,6 +3287,9 @@ static bool frames_op(const fh_problem* p) { return p->op == 12 || p->op == 13; 
 // op 14 (varying blur): ntaps2 counts PSFs and tap2_dy holds their offsets as for the frames, but the measurement keeps the
 // image's size and nothing decimates
 static bool blend_op(const fh_problem* p) { return p->op == 14; }
+// op 15 (Fourier sampling): the mask field carries the weights on the [3][S][S] frequency grid, one map per image, as for ops
+// 8 / 9 - but the head butterfly reads them itself, so the CG keeps no W p vector and the op is not a weighted_op
+static bool hartley_op(const fh_problem* p) { return p->op == 15; }
 static bool decimating_op(const fh_problem* p) {
   return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || frames_op(p);
 }
@@ -3174,8 +3301,8 @@ static int masks_check(const fh_problem* p, const fh_batch& per) {
       if (per.mask[i] != nullptr) return FH_EINVAL;
     return 0;
   }
-  if (weighted_op(p) && p->mask == nullptr) return FH_EINVAL;
-  if (!masked_op(p) && !weighted_op(p)) return 0;
+  if ((weighted_op(p) || hartley_op(p)) && p->mask == nullptr) return FH_EINVAL;
+  if (!masked_op(p) && !weighted_op(p) && !hartley_op(p)) return 0;
   if (per.nimg < 1 || per.nimg > FH_MAX_BATCH) return FH_EINVAL;
   for (int i = 0; i < per.nimg; ++i)
     if (per.mask[i] == nullptr) return FH_EINVAL;
@@ -3313,6 +3440,29 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     }
     return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, So, 1, u, p->sigma_y2, states, st, mtab,
                            dot_part, kCgScratch, dot_nparts);
+  }
+  if (hartley_op(p)) {
+    // Fourier sampling, A0 = H = R o (Hc . Hc) with Hc folded into the DCT bases (P = C_dct Hc, or Hc itself on the identity
+    // basis):  out = sigma_y^2 u + W R( P^T (C (P R(W u) P^T)) P ).  The head butterfly reads u and the weights itself (uin is
+    // not used: the CG keeps no W p vector for this op), the tail one finishes fma(sigma_y^2, u, w * R(t)) and the p.Ap partials.
+    if (planes > ctx->planes_max) return FH_ESIZE;
+    if (!aligned16(u, out) || u == out) return FH_EINVAL;  // 16-byte accesses; the tail butterfly reads u while it writes out
+    for (int i = 0; i < nimg; ++i)
+      if (!aligned16(per.mask[i])) return FH_EINVAL;
+    rc = hartley_launch(ctx, u, w1, planes, &per, nullptr, 0, nullptr, 0.0, states, st);
+    if (rc) return rc;
+    if (p->m == 0) {
+      rc = dct_rect_launch(ctx, w1, w0, planes, p->fold_fwd_w, p->fold_fwd_h, S, 0, nullptr, 0.0, states, st, &per);
+      if (rc) return rc;
+    } else {
+      rc = dct_rect_launch(ctx, w1, w1, planes, p->fold_fwd_w, p->fold_fwd_h, S, 0, nullptr, 0.0, states, st);
+      if (rc) return rc;
+      rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
+      if (rc) return rc;
+    }
+    rc = dct_rect_launch(ctx, w0, w1, planes, p->fold_inv_w, p->fold_inv_h, S, 1, nullptr, 0.0, states, st);
+    if (rc) return rc;
+    return hartley_launch(ctx, w1, out, planes, nullptr, &per, 0, u, p->sigma_y2, states, st, dot_part, kCgScratch, dot_nparts);
   }
   const int halo = p->halo;
   const dim3 egrid(512, 1, (unsigned)nimg);
@@ -3819,6 +3969,37 @@ int fh_dct_rect(fh_context* ctx, const double* in, double* out, const double* P_
                 int inverse, void* stream) {
   if (!ctx || !in || !out || !P_w || !P_h) return FH_EINVAL;
   return dct_rect_launch(ctx, in, out, planes, P_w, P_h, So, inverse != 0, nullptr, 0.0, nullptr, (hipStream_t)stream);
+}
+
+int fh_hartley_fix(fh_context* ctx, const double* in, double* out, const double* w, const double* add, double add_scale,
+                   int planes, void* stream) {
+  if (!ctx || !in || !out || in == out || planes < 1 || planes > 65535) return FH_EINVAL;
+  if (add == out || w == out) return FH_EINVAL;  // (the kernel's operands are __restrict__)
+  if (!aligned16(in, out) || !aligned16(w, add)) return FH_EINVAL;  // 16-byte accesses
+  fh_batch wt;
+  memset(&wt, 0, sizeof(wt));
+  wt.nimg = 1, wt.mask[0] = w;
+  return hartley_launch(ctx, in, out, planes, nullptr, w != nullptr ? &wt : nullptr, 1, add, add_scale, nullptr,
+                        (hipStream_t)stream);
+}
+
+int fh_hartley2d(fh_context* ctx, const double* in, double* out, const double* Hc, int planes, void* stream) {
+  if (!ctx || !in || !out || !Hc || planes < 1 || planes > 65535) return FH_EINVAL;
+  if (!aligned16(out)) return FH_EINVAL;
+  if (planes > ctx->planes_max) return FH_ESIZE;
+  const int rc = dct_rect_launch(ctx, in, ctx->w0, planes, Hc, Hc, ctx->S, 0, nullptr, 0.0, nullptr, (hipStream_t)stream);
+  if (rc) return rc;
+  return hartley_launch(ctx, ctx->w0, out, planes, nullptr, nullptr, 0, nullptr, 0.0, nullptr, (hipStream_t)stream);
+}
+
+int fh_hartley2d_plan(int S, int planes, int32_t out[15]) {
+  if (out == nullptr) return FH_EINVAL;
+  memset(out, 0, sizeof(int32_t) * 15);
+  const int rc = fh_dct_rect_plan(S, S, planes, 0, out);
+  if (rc) return rc;
+  const hartley_plan_t pn = hartley_plan(S, planes);
+  out[10] = pn.gx, out[11] = pn.gy, out[12] = 1, out[13] = 256, out[14] = (int32_t)pn.lds_bytes;
+  return 0;
 }
 
 int fh_dct2d(fh_context* ctx, const double* in, double* out, int planes, int inverse, void* stream) {
@@ -4477,6 +4658,16 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
       hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->cg_wp,
                          n, (const fh_cg_state*)nullptr);
       rc = amm_launch(ctx, p, per, b, ap, nullptr, st, nullptr, nullptr, ctx->cg_wp);
+      if (rc) return rc;
+    }
+  } else if (hartley_op(p)) {
+    // Fourier sampling: sizes and alignment are refused here, before k_cg_init - with cg_scipy no apply precedes it
+    if (p->planes != 3 || p->d != n || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
+    if (!aligned16(b, x)) return FH_EINVAL;  // 16-byte accesses (the weights: masks_check found them non-null)
+    for (int i = 0; i < nimg; ++i)
+      if (!aligned16(per.mask[i])) return FH_EINVAL;
+    if (!p->cg_scipy) {
+      rc = amm_launch(ctx, p, per, b, ap, nullptr, st);
       if (rc) return rc;
     }
   } else if (!p->cg_scipy) {

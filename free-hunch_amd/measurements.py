@@ -1020,6 +1020,249 @@ class WeightedBurstSROperator(_NoiseMap, BurstSROperator):
         return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
 
 
+def folded_dct_hartley_bases(S, use_dct=True):
+    """The bases of `fourier_sampling` (fh_problem.op = 15), float64 (Hc, P), C-contiguous [S][S]:
+        Hc[u][n] = (cos + sin)(2 pi u n / S) / sqrt(S)      symmetric, Hc Hc = I;
+        P        = C_dct Hc  (use_dct)  or  Hc              what folds into the solver's dense passes.
+    The 2-D discrete Hartley transform H x = Re F x - Im F x (F orthonormal) is R(Hc x Hc) with the butterfly R of
+    fh_hartley_fix, so dct2(H u) = P R(u) P^T and H (idct2 v) = R(P^T v P).  Built in extended precision like
+    `dct_basis_longdouble` - the angle reduced with the integer (u n) mod S before it meets 2 pi / S - and rounded once."""
+    S = int(S)
+    if S < 2 or S % 2:
+        raise ValueError(f"folded_dct_hartley_bases: the side must be even and >= 2, got {S}")
+    ld = np.longdouble
+    k = (np.arange(S, dtype=np.int64)[:, None] * np.arange(S, dtype=np.int64)[None, :]) % S
+    ang = k.astype(ld) * (2 * np.arccos(ld(-1)) / ld(S))
+    Hc = (np.cos(ang) + np.sin(ang)) / np.sqrt(ld(S))
+    P = dct_basis_longdouble(S) @ Hc if use_dct else Hc
+    f = lambda M: np.ascontiguousarray(M.astype(np.float64))
+    return f(Hc), f(P)
+
+
+def _reflect(a):
+    """a[..., (-u) % S, (-v) % S]: the point reflection of an FFT-ordered grid about DC"""
+    return np.roll(np.flip(a, axis=(-2, -1)), 1, axis=(-2, -1))
+
+
+KSPACE_PATTERNS = ("cartesian", "radial")
+
+
+def kspace_mask(S, pattern="cartesian", acceleration=4.0, center_fraction=0.08, seed=0):
+    """A 0/1 sampling mask on the [S, S] frequency grid in FFT order (DC at [0, 0], -u = (S - u) % S), float64.
+      cartesian  whole lines along the second axis (u fixed): the centre band |u| <= h with 2 h + 1 the odd count nearest to
+                 center_fraction * S, plus lines outside it drawn at random in +-u pairs until the sampled fraction is
+                 1 / acceleration + center_fraction to within one line (all lines when that asks for more than there are)
+      radial     ceil(S / acceleration) straight spokes through DC at evenly spaced angles with one random offset;
+                 `center_fraction` is not read
+    Both are symmetric under the point reflection k -> -k by construction (a real image's sample at k is its sample at -k),
+    sample DC, and are deterministic in `seed`."""
+    S = int(S)
+    if S < 2 or S % 2:
+        raise ValueError(f"kspace_mask: the side must be even and >= 2, got {S}")
+    if pattern not in KSPACE_PATTERNS:
+        raise ValueError(f"kspace_mask: the pattern is one of {', '.join(KSPACE_PATTERNS)}, got {pattern!r}")
+    try:
+        acc, cf = float(acceleration), float(center_fraction)
+    except (TypeError, ValueError):
+        raise ValueError(f"kspace_mask: acceleration and center_fraction are numbers, got {acceleration!r}, {center_fraction!r}") from None
+    if not (np.isfinite(acc) and acc >= 1.0):
+        raise ValueError(f"kspace_mask: acceleration is a finite number >= 1, got {acceleration!r}")
+    if not (np.isfinite(cf) and 0.0 <= cf < 1.0):
+        raise ValueError(f"kspace_mask: center_fraction is in [0, 1), got {center_fraction!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError(f"kspace_mask: seed is a non-negative integer, got {seed!r}")
+    rng = np.random.default_rng(int(seed))
+    m = np.zeros((S, S))
+    if pattern == "cartesian":
+        h = min(max(int(round((cf * S - 1.0) / 2.0)), 0), S // 2 - 1)
+        lines = np.zeros(S, dtype=bool)
+        lines[np.minimum(np.arange(S), S - np.arange(S)) <= h] = True  # DC and the pairs +-1 .. +-h
+        pool = np.arange(h + 1, S // 2)  # the proper pairs (u, S - u) outside the band; S / 2 is its own reflection
+        pairs = int(round((S * (1.0 / acc + cf) - (2 * h + 1)) / 2.0))
+        if pairs >= pool.size:
+            lines[:] = True
+        elif pairs > 0:
+            u = rng.choice(pool, size=pairs, replace=False)
+            lines[u] = True
+            lines[S - u] = True
+        m[lines, :] = 1.0
+        return m
+    n = int(np.ceil(S / acc))
+    theta = np.pi * (np.arange(n) + rng.random()) / n
+    t = np.arange(0.0, S / 2 + 0.25, 0.5)  # half a spoke; the other half is its reflection
+    u = np.rint(t[None, :] * np.cos(theta)[:, None]).astype(np.int64).ravel()
+    v = np.rint(t[None, :] * np.sin(theta)[:, None]).astype(np.int64).ravel()
+    m[u % S, v % S] = 1.0
+    m[(-u) % S, (-v) % S] = 1.0
+    return m
+
+
+def _kspace_sigma(sigma, S, what):
+    s = np.asarray(sigma, dtype=np.float64)
+    if s.ndim == 0:
+        s = np.full((S, S), float(s))
+    if s.shape != (S, S) or np.isnan(s).any() or not (s > 0).all():
+        raise ValueError(f"{what}: sigma is a number > 0 or an [{S}, {S}] map of such (inf = not measured)")
+    return s
+
+
+def kspace_to_hartley(F, mask, sigma):
+    """Complex k-space samples -> the Hartley-domain measurement of `fourier_sampling`.
+      F      complex [..., S, S], orthonormal DFT samples in FFT order; read only where `mask` is 1
+      mask   0/1 [S, S]: which samples were taken (need not be symmetric)
+      sigma  the noise level PER COMPONENT (real and imaginary part each), a number or an [S, S] map
+    Returns (y, mask_sym, noise_map): y real [..., S, S] with y[k] = Re F~[k] - Im F~[k] (0 off the mask), mask_sym the mask OR
+    its point reflection, noise_map float64 [S, S] (inf off the mask).  F~ is the Hermitian completion: (H[k], H[-k]) is the
+    rotation of (Re F[k], Im F[k]) scaled by sqrt 2, so
+      only one of k, -k measured   the conjugate is filled in; both Hartley entries get sqrt(2) sigma
+      both measured                they are averaged, (F[k] + conj F[-k]) / 2; the entries get sqrt((s_k^2 + s_-k^2) / 2) = sigma
+      k = -k (self-conjugate)      the imaginary part is dropped; the entry gets sigma"""
+    F = np.asarray(F)
+    S = F.shape[-1]
+    if F.ndim < 2 or F.shape[-2] != S or S % 2:
+        raise ValueError(f"kspace_to_hartley: F must be [..., S, S] with S even, got shape {tuple(F.shape)}")
+    m = np.asarray(mask, dtype=np.float64)
+    if m.shape != (S, S) or not np.isin(m, (0.0, 1.0)).all():
+        raise ValueError(f"kspace_to_hartley: the mask must be a 0/1 array of shape ({S}, {S})")
+    s = _kspace_sigma(sigma, S, "kspace_to_hartley")
+    m = m * np.isfinite(s)
+    if not m.any():
+        raise ValueError("kspace_to_hartley: no sample is measured")
+    mr, sr = _reflect(m), _reflect(np.where(m > 0, s, 0.0))
+    s = np.where(m > 0, s, 0.0)
+    Fm = np.where(m > 0, F.astype(np.complex128), 0.0)
+    Fr = np.conj(_reflect(Fm))  # conj F[-k], 0 where -k was not measured
+    cnt = m + mr
+    Ft = (Fm + Fr) / np.maximum(cnt, 1.0)
+    idx = np.arange(S)
+    selfc = ((idx[:, None] * 2) % S == 0) & ((idx[None, :] * 2) % S == 0)
+    var = np.where(cnt == 2, (s ** 2 + sr ** 2) / 2.0, 2.0 * (s ** 2 + sr ** 2))  # one measured: 2 sigma^2 (the other term is 0)
+    var = np.where(selfc, s ** 2, var)
+    msym = (cnt > 0).astype(np.float64)
+    y = np.where(msym > 0, Ft.real - Ft.imag, 0.0)
+    return y, msym, np.where(msym > 0, np.sqrt(var), np.inf)
+
+
+def hartley_to_kspace(y, mask=None):
+    """The inverse of `kspace_to_hartley`: F[k] = (H[k] + H[-k]) / 2 + i (H[-k] - H[k]) / 2, complex128 [..., S, S] (times `mask`,
+    the symmetric 0/1 mask, when one is given)."""
+    y = np.asarray(y, dtype=np.float64)
+    yr = _reflect(y)
+    F = 0.5 * (y + yr) + 0.5j * (yr - y)
+    return F if mask is None else F * np.asarray(mask, dtype=np.float64)
+
+
+_HARTLEY_CACHE = {}
+
+
+@register_operator(name="fourier_sampling")
+class FourierSamplingOperator(_NoiseMap, LinearOperator):
+    """Undersampled Fourier-domain measurement, y = M (H x + n): H the orthonormal 2-D discrete Hartley transform
+    H x = Re F x - Im F x per channel - real, symmetric, self-inverse, and an exact re-expression of k-space data (a sample at k
+    with iid complex noise is the two Hartley samples at k and -k with iid noise; `kspace_to_hartley` converts) - and M a 0/1
+    sampling mask on the [S, S] frequency grid in FFT order (DC at [0, 0]).  Covers Cartesian and radial k-space undersampling
+    and aperture-synthesis uv coverage with one weight per visibility.  Exactly one mask source:
+      mask       array / tensor [S,S], [3,S,S] or [1,3,S,S], entries exactly 0 or 1
+      mask_path  a .npy of the same shapes
+      pattern    "cartesian" or "radial": `kspace_mask(S, pattern, acceleration, center_fraction, seed)`
+    The mask is made symmetric by OR with its point reflection m[-u][-v]: for a real image a sample at k IS a sample at -k (its
+    conjugate), so both Hartley entries are known.  An all-zero mask is refused.  Optional `noise_map` / `noise_map_path`: the
+    per-entry noise level on the same grid, `_NoiseMap`'s rules (entries > 0 or +inf, floor 0.001); entries off the mask count as
+    inf.  `weights` is always present - the mask, or 1 / noise_map (0 off the mask or where inf) - and is what the solver
+    whitens with (fh_problem.op = 15; sigma_y2 = clip(sigma_s, 0.001)^2 without a map, 1 with one).
+    `forward` = mask * (H x + n), `transpose` = `forward_adjoint` = H (mask * v)."""
+
+    def __init__(self, in_shape, sigma_s, device, mask=None, mask_path=None, pattern=None, acceleration=4.0, center_fraction=0.08,
+                 seed=0, noise_map=None, noise_map_path=None, **kwargs):
+        name = self.name
+        S = int(in_shape[-1])
+        if S < 2 or S % 2 or int(in_shape[-2]) != S:
+            raise ValueError(f"{name}: the image must be square with an even side, got {tuple(in_shape)}")
+        mask_path, pattern, noise_map_path = mask_path or None, pattern or None, noise_map_path or None
+        if sum(v is not None for v in (mask, mask_path, pattern)) != 1:
+            raise ValueError(f"{name} needs exactly one of mask (an array), mask_path (a .npy file) and pattern "
+                             f"({' / '.join(KSPACE_PATTERNS)}, with acceleration, center_fraction, seed)")
+        if pattern is not None:
+            a = kspace_mask(S, pattern, acceleration, center_fraction, seed)
+        else:
+            a = np.load(mask_path) if mask is None else (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask))
+        if tuple(a.shape) not in ((S, S), (3, S, S), (1, 3, S, S)):
+            raise ValueError(f"{name}: the mask must have shape ({S}, {S}), (3, {S}, {S}) or (1, 3, {S}, {S}), got {tuple(a.shape)}")
+        a = np.asarray(a, dtype=np.float64)
+        if not np.isin(a, (0.0, 1.0)).all():
+            raise ValueError(f"{name}: the mask has an entry other than 0 and 1 (per-entry noise levels go in noise_map)")
+        m = np.ones((1, 3, S, S)) * a.reshape((1, 1, S, S) if a.ndim == 2 else (1, 3, S, S))
+        m = np.maximum(m, _reflect(m))
+        if not m.any():
+            raise ValueError(f"{name}: the mask is all zero - no frequency is measured")
+        self.device = torch.device(device)
+        self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
+        self.in_shape = in_shape
+        self.out_shape = tuple(in_shape)
+        self.mask = torch.from_numpy(np.ascontiguousarray(m)).to(self.device)  # float64 [1,3,S,S]
+        if noise_map is None and noise_map_path is None:
+            self.noise_map = None
+            self.weights = self.mask
+        else:
+            self._set_noise_map(S, noise_map, noise_map_path)  # noise_map, weights, mask = weights > 0 of the map alone
+            w = self.weights * torch.from_numpy(m).to(self.device)
+            if not bool((w > 0).any()):
+                raise ValueError(f"{name}: no frequency is both on the mask and finite in the noise map")
+            self.noise_map = torch.where(w > 0, self.noise_map, torch.full_like(self.noise_map, float("inf")))
+            self.weights = w.contiguous()
+            self.mask = (w > 0).to(F64)
+
+    def _noise(self, y, noiseless):
+        if self.noise_map is not None:
+            return _NoiseMap._noise(self, y, noiseless)
+        return LinearOperator._noise(self, y, noiseless) * self.mask.to(y.dtype)
+
+    def hartley_basis(self):
+        """Hc of `folded_dct_hartley_bases` on the device, built once per (side, device)"""
+        return self.folded_hartley_bases(False)[0]
+
+    def folded_hartley_bases(self, use_dct, device=None):
+        """device copies (P, P^T) of `folded_dct_hartley_bases` - fold_fwd_* and fold_inv_* of fh_problem.op = 15"""
+        S, dev = int(self.in_shape[-1]), torch.device(device if device is not None else self.device)
+        key = (S, bool(use_dct), str(dev))
+        if key not in _HARTLEY_CACHE:
+            P = folded_dct_hartley_bases(S, use_dct)[1]
+            _HARTLEY_CACHE[key] = (torch.from_numpy(P).to(dev), torch.from_numpy(np.ascontiguousarray(P.T)).to(dev))
+        return _HARTLEY_CACHE[key]
+
+    def _conv(self, x, stride=None, adjoint=False):
+        """H x of an NCHW tensor [N,3,S,S]; float64.  H is its own adjoint and nothing decimates: both arguments are ignored."""
+        S = self.in_shape[-1]
+        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
+        N = x64.shape[0]
+        assert tuple(x64.shape[1:]) == (3, S, S), f"fourier_sampling: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
+        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)
+        return ctx.hartley2d(x64, torch.empty_like(x64), self.hartley_basis())
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # ONE noise draw at the grid's shape, then the mask
+        y = self._noise(self._conv(data).to(data.dtype), noiseless)
+        self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *self.in_shape[-3:])
+        return self._conv(y * self.mask.to(y.dtype)).to(y.dtype)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward`: H (mask * v)"""
+        return self._conv(v * self.mask.to(v.dtype)).to(v.dtype)
+
+    def folded_bases(self):
+        return None
+
+    def folded_sr_bases(self):
+        return None
+
+
 def _cubic(x):
     ax = np.abs(x)
     return ((1.5 * ax ** 3 - 2.5 * ax ** 2 + 1) * (ax <= 1)

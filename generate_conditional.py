@@ -114,6 +114,9 @@ def main(argv=None):
                          mask_path=o.mask_path or None, mask_border=o.mask_border, frame_shifts=o.frame_shifts or None,
                          frame_sigmas=o.frame_sigmas or None, mosaic=o.mosaic or None,
                          blend_path=o.blend_path or None, psf_grid=o.psf_grid or None,
+                         pattern=o.kspace_pattern or None, acceleration=o.kspace_acceleration,
+                         center_fraction=0.08 if o.kspace_center_fraction is None else o.kspace_center_fraction,
+                         seed=0 if o.kspace_seed is None else o.kspace_seed,
                          mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
                                    "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
                                    if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})
@@ -151,7 +154,10 @@ def main(argv=None):
                 **kw)[0].detach() for b in range(len(ops))])
         outs.append(enc.decode(x))
         conds.append(torch.stack(imgs).to(device))
-        fwds += [enc.decode(y) for y in ys]
+        if o.operator_name == "fourier_sampling":  # a frequency grid is no picture: the zero-filled reconstruction A0^T y
+            fwds += [enc.decode(op.transpose(y)) for op, y in zip(ops, ys)]
+        else:
+            fwds += [enc.decode(y) for y in ys]
         print(f"[rank {rank}] (image, seed) {chunk} done", flush=True)
     local_out = torch.cat(outs) if outs else torch.zeros((0, 3, S, S), dtype=torch.uint8, device=device)
     local_cond = torch.cat(conds) if conds else torch.zeros((0, 3, S, S), dtype=torch.uint8, device=device)

@@ -77,6 +77,26 @@ int fh_dct_rect(fh_context* ctx, const double* in, double* out, const double* P_
                 int inverse, void* stream);
 int fh_dct_rect_plan(int S, int So, int planes, int inverse, int32_t out[10]);
 
+/* 2-D discrete Hartley transform H x = Re F x - Im F x (F orthonormal) of `planes` real planes [S][S] at the context's side,
+ * the measurement of fh_problem.op = 15.  The frequency grid is in FFT order: DC at [0][0], -u = (S - u) % S.
+ * With Hc[u][n] = (cos + sin)(2 pi u n / S) / sqrt(S) (symmetric, Hc Hc = I; measurements.py: folded_dct_hartley_bases) and
+ * T = Hc X Hc,  H x = R(T),  R(T)[u][v] = 1/2 ((T[u][v] + T[-u][v]) + (T[u][-v] - T[-u][-v])),  R symmetric, R R = I.
+ *   fh_hartley_fix: out = R(in), one streaming kernel (16-byte accesses; a row pair (u, -u) staged in LDS, the mirrored columns
+ *     read in reverse).  The value is the expression above evaluated in exactly that order.  w != null: out = w .* R(in), the
+ *     weights of plane p at w + (p % 3) S S (one [3][S][S] map for every image); add != null: out = fma(add_scale, add, w * r)
+ *     with w * r rounded.  in == out: FH_EINVAL (the kernel reads reflected positions), and so is add == out or w == out: out must not overlap
+ *     any operand, whole or in part (partial overlaps are not detected).  FH_EINVAL: a null in / out, planes < 1 or
+ *     > 65535, a pointer that is not 16-byte aligned; FH_ESIZE: planes beyond the context's planes_max.
+ *   fh_hartley2d: out = H in = fh_dct_rect at So = S with Hc on both sides, then the butterfly; self-inverse.  in may equal out.
+ *     Writes one of the context's work vectors (as fh_conv_blend: not concurrently with another call on the same context).
+ *   fh_hartley2d_plan: the three launches without a context or a device: out[0 .. 9] as fh_dct_rect_plan(S, S, planes, 0), then
+ *     {grid x, grid y, grid z, block size, dynamic LDS bytes} of the butterfly (zeros on an error).  Its grid x = S / 2 + 1 row
+ *     pairs over as few blocks as walk them in the trips 85 blocks would need, grid y = min(planes, 48) planes per trip. */
+int fh_hartley_fix(fh_context* ctx, const double* in, double* out, const double* w, const double* add, double add_scale,
+                   int planes, void* stream);
+int fh_hartley2d(fh_context* ctx, const double* in, double* out, const double* Hc, int planes, void* stream);
+int fh_hartley2d_plan(int S, int planes, int32_t out[15]);
+
 /* Adds the DCT moments of n images to running sums: the accumulation loop of the DCT-variance prior,
  * do_frequency_analysis.py:40-44.  imgs: uint8 [n][3][S][S] (4-byte aligned); work: n*3*S*S doubles of scratch;
  * sum, sumsq: double [3][S][S], read and written (16-byte aligned, zeroed by the caller before the first call).
@@ -356,6 +376,20 @@ typedef struct fh_problem {
    * ops 2 and 12.  FH_BLEND_FUSED is read as by fh_conv_blend, and the CG graph cache keys on it and on the offsets.  K = 1 with
    * an all-ones map gives the bits of op 1 on its plain tap list; one-hot maps over identical PSFs give, in the FORWARD direction,
    * those of one fh_conv_circ (the adjoint adds K separately rounded pieces and agrees to rounding only).
+   * 15 Fourier sampling: y = M (H x) + n measured in the Hartley domain (fh_hartley2d: a k-space sample at k with iid complex
+   * noise is two Hartley samples, at k and -k, with iid noise), A0 = H = A0^T.  With P = C_dct Hc (use_dct = 1; the host passes
+   * P = Hc with use_dct = 0):  fold_fwd_w = fold_fwd_h = P, fold_inv_w = fold_inv_h = P^T, each [S][S] float64, all four non-null,
+   * fold_sym = 0:  dct2(A0^T u) = P R(u) P^T,  A0 (idct2 v) = R(P^T v P).  mask = the WEIGHTS w >= 0 on the [3][S][S] frequency
+   * grid (FFT order), non-null, every per->mask[i] of a batched solve non-null (one map per image); stride = 1, ntaps = ntaps2 =
+   * halo = halo2 = 0 and every tap pointer null; planes = 3, d = 3 S S.  The semantics of ops 8 .. 11:
+   *   fh_amm:   A_mm(u) = sigma_y2 u + W A0 C A0^T W u for an arbitrary u, = sigma_y2 u exactly where w = 0;
+   *   fh_cg_solve[_batched]: solves for b AS GIVEN (the whitened right-hand side W (y - A0 x0)); mat = A0^T W x.
+   * 0/1 weights with sigma_y2 = s^2 are the plain masked problem, w = 1 / sigma with sigma_y2 = 1 the noise-map problem.
+   * One apply: R(W u) - the head butterfly multiplies the weights into its input ITSELF, so unlike ops 8 .. 11 the CG keeps no
+   * W p vector and runs k_cg_step2 - then the two dense passes forward (D .* in their epilogue at m = 0, else the covariance
+   * apply behind them), the two inverse, and the tail butterfly out = fma(sigma_y2, u, w * R(t)) with w * R(t) rounded, which also
+   * leaves the p.Ap partials (3 x its grid x <= 255 per image, the same blocks and order whatever the batch).  u, out, b, x and
+   * the weights are 16-byte aligned, and fh_amm's out is not u.  Anything else: FH_EINVAL before any launch, in either CG mode.
    * Any other value: FH_EINVAL. */
   int32_t op;
   int32_t use_dct;       /* 1: covariance lives in the DCT basis (CovarianceHessianBFGSDCT) */
@@ -370,7 +404,7 @@ typedef struct fh_problem {
   const int32_t* tap_dy; /* [ntaps] */
   const int32_t* tap_dx;
   const double* tap_w;
-  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement); ops 8 .. 11 and 13: the weights */
+  const double* mask;    /* [d] 0/1 (inpainting; ops 5 / 6: the validity mask of the blurred measurement); ops 8 .. 11, 13 and 15: the weights */
   const double* D;       /* covariance rep: diag, row scale, base, inner matrix */
   const double* r;
   const double* B;
@@ -401,9 +435,9 @@ typedef struct fh_problem {
 } fh_problem;
 
 /* Per-image covariance pointers of a batched solve: B images share the operator, the tap lists, m, ldm and
- * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5, 6, 8 .. 11 and 13 read
- * mask[i], which may differ from image to image (ops 5 / 6 / 8 .. 11 / 13: all non-null, else FH_EINVAL; the PSF is shared; ops
- * 8 .. 11 / 13 also want a non-null fh_problem.mask). */
+ * sigma_y2 of an fh_problem (whose D, r, B, M, mask fields are then ignored) and differ in these.  Ops 0, 5, 6, 8 .. 11, 13 and 15
+ * read mask[i], which may differ from image to image (ops 5 / 6 / 8 .. 11 / 13 / 15: all non-null, else FH_EINVAL; the PSF is
+ * shared; ops 8 .. 11 / 13 / 15 also want a non-null fh_problem.mask). */
 #define FH_MAX_BATCH 16
 typedef struct fh_batch {
   int32_t nimg;
