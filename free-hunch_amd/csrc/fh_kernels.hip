@@ -3223,89 +3223,116 @@ static int window_launch(fh_context* ctx, const double* in, double* out, const d
   return 0;
 }
 
-// fh_problem.op = 4 / 6 (dense-window blur): tap_w is the window, halo = 64 hy + hx, and nothing of the tap-list operators is set
-static int window_problem_check(const fh_problem* p) {
-  const int hy = p->halo / 64, hx = p->halo % 64;
-  if (p->halo < 0 || hy > 32 || hx > 32 || p->ntaps != (2 * hy + 1) * (2 * hx + 1) || p->stride != 1) return FH_EINVAL;
-  if (p->tap_w == nullptr || p->tap_dy || p->tap_dx || p->ntaps2 != 0 || p->tap2_dy || p->tap2_dx || p->tap2_w) return FH_EINVAL;
-  if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
-  return 0;
-}
+// What the solver knows about an operator code, once: kOps[fh_problem.op].  A new operator is one row here, one arm of
+// problem_check and one case of op_apply_launch (or a folded route of its own in amm_launch).
+enum op_apply {      // how A is applied
+  APPLY_MASK,        // A = a 0/1 mask (k_mask; the mask field is the operator itself)
+  APPLY_TAPS,        // tap list through conv_launch; a second list (ntaps2 > 0) is the other factor of a separable PSF
+  APPLY_WINDOW,      // dense window (window_launch): tap_w is the window, halo = 64 hy + hx
+  APPLY_MIX,         // channel mix, one measurement plane per image; commutes with the DCT (its own route)
+  APPLY_RECT,        // rank-1 PSF + decimation folded into rectangular DCT bases (its own route)
+  APPLY_FRAMES,      // K decimated frames (frames_launch): ntaps2 counts frames, tap2_dy holds their offsets
+  APPLY_BLEND,       // K blended PSFs (blend_launch): the same two fields and the maps in tap2_w; nothing decimates
+  APPLY_HARTLEY      // Fourier sampling on folded Hartley bases (its own route)
+};
+enum op_mask {        // what the mask field (and per.mask[i] of a batch) means
+  MASK_IGNORED,       // no check reads it (op 0 reads it as its operator)
+  MASK_NULL,          // refused unless null: no mask on a low-resolution measurement, none on the varying blur
+  MASK_VALID,         // 0/1 validity mask, one per image: idempotent, so only the first apply needs the input side
+  MASK_WEIGHTS_WP,    // noise map w = 1 / sigma in the measurement's own layout ([3][n][n] per image at its side n, op 13:
+                      // [K][3][So][So], frame-major); the operator reads W p, which the CG keeps beside p (cg_wp)
+  MASK_WEIGHTS_SELF   // weights on the [3][S][S] frequency grid that the head butterfly reads itself: the CG keeps no W p
+};
+enum op_meas { MEAS_ONE_PLANE, MEAS_IMAGE, MEAS_PER_FRAME };  // measurement planes per image: 1, 3, 3 K (K = ntaps2 frames)
+struct op_facts {
+  op_apply apply;
+  op_mask mask;           // (MASK_NULL: problem_check refuses p->mask, masks_check every per.mask[i])
+  bool decimated;        // the measurement's side is S / stride
+  op_meas meas;
+  bool foldable;          // a separable blur that the DCT bases can absorb (fold_* set, use_dct)
+  bool dot_partials;      // a route of this op hands the p.Ap block partials back from its last pass
+  bool align16;           // the op's kernels read u and write out with 16-byte accesses
+  bool unchecked;         // ops 0 .. 3 predate problem_check: their launch plans refuse what they cannot run
+  bool (*graph_route)();  // non-null: a chain route bakes host-read offsets into a captured graph; its A/B switch (cg_graph_for)
+};
+constexpr int kNumOps = 16;
+static const op_facts kOps[kNumOps] = {
+    // apply         mask               decim. meas            fold   dot    al16   unchk  graph_route
+    {APPLY_MASK,    MASK_IGNORED,      false, MEAS_IMAGE,     false, false, false, true,  nullptr},          //  0 inpainting, denoising
+    {APPLY_TAPS,    MASK_IGNORED,      false, MEAS_IMAGE,     true,  true,  false, true,  nullptr},          //  1 blur
+    {APPLY_TAPS,    MASK_IGNORED,      true,  MEAS_IMAGE,     false, false, false, true,  nullptr},          //  2 super-resolution
+    {APPLY_MIX,     MASK_IGNORED,      false, MEAS_ONE_PLANE, false, true,  true,  true,  nullptr},          //  3 colorization
+    {APPLY_WINDOW,  MASK_IGNORED,      false, MEAS_IMAGE,     false, false, false, false, nullptr},          //  4 dense-window blur
+    {APPLY_TAPS,    MASK_VALID,        false, MEAS_IMAGE,     true,  true,  false, false, nullptr},          //  5 masked op 1
+    {APPLY_WINDOW,  MASK_VALID,        false, MEAS_IMAGE,     false, false, false, false, nullptr},          //  6 masked op 4
+    {APPLY_RECT,    MASK_NULL,         true,  MEAS_IMAGE,     false, true,  false, false, nullptr},          //  7 folded SR
+    {APPLY_TAPS,    MASK_WEIGHTS_WP,   false, MEAS_IMAGE,     true,  true,  false, false, nullptr},          //  8 op 1 + noise map
+    {APPLY_WINDOW,  MASK_WEIGHTS_WP,   false, MEAS_IMAGE,     false, false, false, false, nullptr},          //  9 op 4 + noise map
+    {APPLY_TAPS,    MASK_WEIGHTS_WP,   true,  MEAS_IMAGE,     false, false, false, false, nullptr},          // 10 op 2 + noise map
+    {APPLY_RECT,    MASK_WEIGHTS_WP,   true,  MEAS_IMAGE,     false, true,  false, false, nullptr},          // 11 op 7 + noise map
+    {APPLY_FRAMES,  MASK_NULL,         true,  MEAS_PER_FRAME, false, false, false, false, frames_fused_on},  // 12 multi-frame SR
+    {APPLY_FRAMES,  MASK_WEIGHTS_WP,   true,  MEAS_PER_FRAME, false, false, false, false, frames_fused_on},  // 13 op 12 + noise map
+    {APPLY_BLEND,   MASK_NULL,         false, MEAS_IMAGE,     false, false, false, false, blend_fused_on},   // 14 varying blur
+    {APPLY_HARTLEY, MASK_WEIGHTS_SELF, false, MEAS_IMAGE,     false, true,  true,  false, nullptr},          // 15 Fourier sampling
+};
+// (after problem_check has found the op in range)
+static const op_facts& facts(const fh_problem* p) { return kOps[p->op]; }
+// the one choice between k_cg_init_w / k_cg_step2_w, which write W p beside p, and the plain k_cg_init / k_cg_step2
+static bool cg_keeps_wp(const fh_problem* p) { return facts(p).mask == MASK_WEIGHTS_WP; }
 
-// what fh_amm / fh_cg_solve[_batched] refuse before anything is launched
-// (the masks of a batched solve are per->mask[i]: masks_check)
-// S: the context's image side
+// what fh_amm / fh_cg_solve[_batched] refuse before anything is launched: one arm per field layout
+// (the masks of a batched solve are per->mask[i]: masks_check);  S: the context's image side
 static int problem_check(const fh_problem* p, int S) {
-  if (p->op < 0 || p->op > 15) return FH_EINVAL;
-  if (p->op == 15) {  // Fourier sampling: the four [S][S] folded Hartley bases and the weights, nothing of the tap-list operators
-    if (p->stride != 1 || (p->use_dct != 0 && p->use_dct != 1) || p->fold_sym != 0 || p->mask == nullptr) return FH_EINVAL;
-    if (!p->fold_fwd_w || !p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
-    if (p->ntaps != 0 || p->ntaps2 != 0 || p->halo != 0 || p->halo2 != 0) return FH_EINVAL;
-    if (p->tap_dy || p->tap_dx || p->tap_w || p->tap2_dy || p->tap2_dx || p->tap2_w) return FH_EINVAL;
-    return 0;
+  if (p->op < 0 || p->op >= kNumOps) return FH_EINVAL;
+  const op_facts& f = kOps[p->op];
+  if (f.unchecked) return 0;
+  if (f.mask == MASK_NULL && p->mask != nullptr) return FH_EINVAL;
+  const bool no_folds = !p->fold_fwd_w && !p->fold_fwd_h && !p->fold_inv_w && !p->fold_inv_h;
+  const bool all_folds = p->fold_fwd_w && p->fold_fwd_h && p->fold_inv_w && p->fold_inv_h;
+  switch (f.apply) {
+    case APPLY_HARTLEY:  // the four [S][S] folded Hartley bases and the weights, nothing of the tap-list operators
+      if (p->stride != 1 || (p->use_dct != 0 && p->use_dct != 1) || p->fold_sym != 0 || p->mask == nullptr) return FH_EINVAL;
+      if (!all_folds || p->ntaps != 0 || p->ntaps2 != 0 || p->halo != 0 || p->halo2 != 0) return FH_EINVAL;
+      return p->tap_dy || p->tap_dx || p->tap_w || p->tap2_dy || p->tap2_dx || p->tap2_w ? FH_EINVAL : 0;
+    case APPLY_BLEND: {  // ntaps2 = K PSFs, tap2_dy = their offsets, halo2 = the longest list, tap2_w = the blend maps
+      const int K = p->ntaps2;
+      conv_extent e;
+      if (p->stride != 1 || K < 1 || K > 16 || (p->use_dct != 0 && p->use_dct != 1)) return FH_EINVAL;
+      if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
+      if (p->halo < 1000 || conv_decode(p->halo, &e) != 0) return FH_EINVAL;
+      if (!p->tap2_dy || !p->tap2_w || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
+      return p->tap2_dx || p->fold_sym != 0 || !no_folds ? FH_EINVAL : 0;
+    }
+    case APPLY_FRAMES: {  // stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
+      const int s = p->stride, K = p->ntaps2;
+      if (s < 2 || s > 4 || S % s != 0 || K < 1 || K > s * s) return FH_EINVAL;
+      if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
+      if (p->halo < 1000 || p->tap2_dy == nullptr || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
+      return p->tap2_dx || p->tap2_w || p->fold_sym != 0 || !no_folds ? FH_EINVAL : 0;
+    }
+    case APPLY_RECT:  // the four [S][S / stride] / [S / stride][S] bases; the tap fields are not read
+      return p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0 || !all_folds ? FH_EINVAL : 0;
+    case APPLY_WINDOW: {  // tap_w is the window, halo = 64 hy + hx, and nothing of the tap-list operators is set
+      const int hy = p->halo / 64, hx = p->halo % 64;
+      if (p->halo < 0 || hy > 32 || hx > 32 || p->ntaps != (2 * hy + 1) * (2 * hx + 1) || p->stride != 1) return FH_EINVAL;
+      if (p->tap_w == nullptr || p->tap_dy || p->tap_dx || p->ntaps2 != 0 || p->tap2_dy || p->tap2_dx || p->tap2_w) return FH_EINVAL;
+      return no_folds ? 0 : FH_EINVAL;
+    }
+    case APPLY_TAPS:  // stride 1, or a true decimation (op 10: the tap list of op 2)
+      return (f.decimated ? p->stride < 2 || S % p->stride != 0 : p->stride != 1) ? FH_EINVAL : 0;
+    default: return 0;
   }
-  if (p->op == 14) {  // varying blur: ntaps2 = K PSFs, tap2_dy = their offsets, halo2 = the longest list, tap2_w = the blend maps
-    const int K = p->ntaps2;
-    conv_extent e;
-    if (p->stride != 1 || K < 1 || K > 16 || (p->use_dct != 0 && p->use_dct != 1)) return FH_EINVAL;
-    if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
-    if (p->halo < 1000 || conv_decode(p->halo, &e) != 0) return FH_EINVAL;
-    if (!p->tap2_dy || !p->tap2_w || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
-    if (p->tap2_dx || p->mask || p->fold_sym != 0) return FH_EINVAL;
-    if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
-    return 0;
-  }
-  if (p->op == 12 || p->op == 13) {  // multi-frame SR: stride = s, ntaps2 = K frames, tap2_dy = their offsets, halo2 = the longest frame
-    // (op 13 brings the weights in mask: masks_check refuses a null one)
-    const int s = p->stride, K = p->ntaps2;
-    if (s < 2 || s > 4 || S % s != 0 || K < 1 || K > s * s) return FH_EINVAL;
-    if (p->halo2 < 1 || p->halo2 > kMaxTaps || p->ntaps < K || p->ntaps > K * p->halo2) return FH_EINVAL;
-    if (p->halo < 1000 || p->tap2_dy == nullptr || !p->tap_dy || !p->tap_dx || !p->tap_w) return FH_EINVAL;
-    if (p->tap2_dx || p->tap2_w || (p->op == 12 && p->mask) || p->fold_sym != 0) return FH_EINVAL;
-    if (p->fold_fwd_w || p->fold_fwd_h || p->fold_inv_w || p->fold_inv_h) return FH_EINVAL;
-    return 0;
-  }
-  if (p->op == 7 || p->op == 11) {  // separable SR on folded rectangular bases: the four [S][S / stride] / [S / stride][S] bases
-    if (p->stride < 2 || S % p->stride != 0 || !p->use_dct || p->fold_sym != 0) return FH_EINVAL;
-    if (p->op == 7 && p->mask != nullptr) return FH_EINVAL;  // no mask on the low-resolution measurement (the weights: op 11)
-    if (!p->fold_fwd_w || !p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
-    return 0;
-  }
-  if (p->op == 10) return p->stride < 2 || S % p->stride != 0 ? FH_EINVAL : 0;  // the tap list of op 2 at a true decimation
-  if (p->op >= 5 && p->stride != 1) return FH_EINVAL;
-  return p->op == 4 || p->op == 6 || p->op == 9 ? window_problem_check(p) : 0;
 }
 
-// ops 5 / 6 (masked blur): every image of the batch brings a mask
-static bool masked_op(const fh_problem* p) { return p->op == 5 || p->op == 6; }
-// ops 8 .. 11 (per-pixel noise map): the mask field carries the weights w = 1 / sigma, [3][n][n] per image at the
-// measurement's side n (S for ops 8 / 9, S / stride for ops 10 / 11)
-// op 13 (the noise map on the burst of op 12): [K][3][So][So] per image, the measurement's own frame-major layout
-static bool weighted_op(const fh_problem* p) { return (p->op >= 8 && p->op <= 11) || p->op == 13; }
-// ops 12 / 13 (multi-frame SR): ntaps2 counts frames, tap2_dy holds their offsets
-static bool frames_op(const fh_problem* p) { return p->op == 12 || p->op == 13; }
-// op 14 (varying blur): ntaps2 counts PSFs and tap2_dy holds their offsets as for the frames, but the measurement keeps the
-// image's size and nothing decimates
-static bool blend_op(const fh_problem* p) { return p->op == 14; }
-// op 15 (Fourier sampling): the mask field carries the weights on the [3][S][S] frequency grid, one map per image, as for ops
-// 8 / 9 - but the head butterfly reads them itself, so the CG keeps no W p vector and the op is not a weighted_op
-static bool hartley_op(const fh_problem* p) { return p->op == 15; }
-static bool decimating_op(const fh_problem* p) {
-  return p->op == 2 || p->op == 7 || p->op == 10 || p->op == 11 || frames_op(p);
-}
-// measurement planes per image: one for colorization, 3 K for the K frames of ops 12 / 13, else 3
-static int meas_planes(const fh_problem* p) { return p->op == 3 ? 1 : (frames_op(p) ? p->ntaps2 : 1) * p->planes; }
+// per.mask[i] of every image of the batch against the op's rule (fh_amm: the one mask of the problem)
 static int masks_check(const fh_problem* p, const fh_batch& per) {
-  if (p->op == 7 || p->op == 12 || p->op == 14) {  // no mask on the low-resolution measurement, none on the varying blur
-    for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
-      if (per.mask[i] != nullptr) return FH_EINVAL;
-    return 0;
-  }
-  if ((weighted_op(p) || hartley_op(p)) && p->mask == nullptr) return FH_EINVAL;
-  if (!masked_op(p) && !weighted_op(p) && !hartley_op(p)) return 0;
-  if (per.nimg < 1 || per.nimg > FH_MAX_BATCH) return FH_EINVAL;
-  for (int i = 0; i < per.nimg; ++i)
-    if (per.mask[i] == nullptr) return FH_EINVAL;
+  const op_mask rule = facts(p).mask;
+  if (rule == MASK_IGNORED) return 0;
+  const bool want = rule != MASK_NULL;  // every image with a mask, or (MASK_NULL) every image without one
+  // (weights also come in p->mask; a batch of masked blurs brings its masks in per alone)
+  if (want && ((rule != MASK_VALID && p->mask == nullptr) || per.nimg < 1 || per.nimg > FH_MAX_BATCH)) return FH_EINVAL;
+  for (int i = 0; i < per.nimg && i < FH_MAX_BATCH; ++i)
+    if ((per.mask[i] != nullptr) != want) return FH_EINVAL;
   return 0;
 }
 
@@ -3319,7 +3346,7 @@ static std::mutex g_capture_mu;
 
 // colorization with no factor columns on the symmetric DCT passes: A C A^T is diagonal in the DCT basis (D_eff)
 static bool colorize_deff_route(const fh_context* ctx, const fh_problem* p) {
-  return p->op == 3 && p->use_dct && p->m == 0 && sym_dct(ctx);
+  return facts(p).apply == APPLY_MIX && p->use_dct && p->m == 0 && sym_dct(ctx);
 }
 
 // once per solve (and per fh_amm call): D_eff of every image into the context's scratch, before the first apply
@@ -3337,6 +3364,84 @@ static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch
                      p->tap_w, ctx->deff, pairs);
   FH_LAUNCH_CHECK();
   return 0;
+}
+
+// One application of the operator, for the kinds that have kernels of their own: out = A^T in (`adjoint`; no add, no masks),
+// or out = add_scale * add + A in, with the mask / weights of `masks` (null: none) multiplied into A in by the pass that
+// finishes it.  spare: a work vector that is neither in nor out nor add.  The first pass of a separable PSF writes it, the
+// chains of ops 12 .. 14 go through it, and so does every pass that has no masked epilogue.  Forward, `in` is a work vector
+// as well and is free once it has been read.
+static int op_apply_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, int adjoint, const double* in,
+                           double* out, double* spare, const double* add, double add_scale, const fh_batch* masks,
+                           const fh_cg_state* states, hipStream_t st) {
+  const int planes = p->planes * per.nimg, halo = p->halo;
+  switch (facts(p).apply) {
+    case APPLY_MASK:
+      hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)per.nimg), dim3(256), 0, st, per, in, add, add_scale, out, p->d, states);
+      FH_LAUNCH_CHECK();
+      return 0;
+    case APPLY_WINDOW:
+      return window_launch(ctx, in, out, p->tap_w, halo / 64, halo % 64, planes, adjoint, add, add_scale, states, st, masks);
+    case APPLY_FRAMES:
+      return frames_launch(ctx, in, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
+                           p->stride, adjoint, add, add_scale, states, st, masks, spare);
+    case APPLY_BLEND:
+      return blend_launch(ctx, in, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
+                          adjoint, p->tap2_w, add, add_scale, states, st, spare);
+    case APPLY_TAPS: {
+      if (p->ntaps2 <= 0)  // one list, at any stride
+        return conv_launch(ctx, in, out, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, adjoint, add,
+                           add_scale, states, st, masks, spare);
+      // separable PSF: two 1-D passes through `spare` (blur only, stride 1: amm_launch refuses another), the second list first
+      // on the way back; the pass that finishes takes the add, the masks and - `in` has been read - in as its own spare
+      const auto pass = [&](bool second, const double* i, double* o, const double* a, double as, const fh_batch* mk, double* sp) {
+        return second ? conv_launch(ctx, i, o, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, adjoint, a, as,
+                                    states, st, mk, sp)
+                      : conv_launch(ctx, i, o, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, adjoint, a, as, states, st,
+                                    mk, sp);
+      };
+      const int rc = pass(adjoint, in, spare, nullptr, 0.0, nullptr, nullptr);
+      return rc ? rc : pass(!adjoint, spare, out, add, add_scale, masks, const_cast<double*>(in));
+    }
+    default: return FH_EINVAL;  // the mix and the folded operators have routes of their own (amm_launch)
+  }
+}
+
+// The covariance inside a folded forward pass (the folded symmetric blur on k_dct_sym: `sym`; ops 7 / 11 and op 15 on
+// k_dct_rect):  w0 = C dct2(A^T in).  With no factor columns (every call above sigma = 10, i.e. three quarters of all CG
+// iterations of a Heun-30 run) C z = D .* z rides in the epilogue of the forward pass - two kernels instead of three; else
+// the plain pass goes to w1 (in place where in is w1) and rep_apply_launch brings it to w0.
+static int cov_in_dct_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* in, bool sym,
+                             const fh_cg_state* states, hipStream_t st) {
+  const int planes = p->planes * per.nimg;
+  const auto forward = [&](double* out, const fh_batch* diag) {
+    if (sym) return dct2d_launch_sym(ctx, in, out, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st, diag);
+    return dct_rect_launch(ctx, in, out, planes, p->fold_fwd_w, p->fold_fwd_h, ctx->S / p->stride, 0, nullptr, 0.0, states, st,
+                           diag);
+  };
+  if (p->m == 0) return forward(ctx->w0, &per);
+  const int rc = forward(ctx->w1, nullptr);
+  return rc ? rc : rep_apply_launch(ctx, per, p->ldm, ctx->w1, ctx->w0, p->d, p->m, states, st);
+}
+
+// The covariance of the generic route, through the DCT basis when it lives there:  *w1 = C *w0.  The symmetric passes carry
+// the diagonal-only covariance in the forward pass's epilogue and come back into the vector they started from: the two
+// pointers then swap, so that the caller finds the result in *w1 and a free vector in *w0 on every route.
+static int cov_apply_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, double** w0, double** w1,
+                            const fh_cg_state* states, hipStream_t st) {
+  const int planes = p->planes * per.nimg;
+  if (!p->use_dct) return rep_apply_launch(ctx, per, p->ldm, *w0, *w1, p->d, p->m, states, st);  // identity basis
+  if (p->m == 0 && sym_dct(ctx)) {
+    int rc = dct2d_launch_sym(ctx, *w0, *w1, planes, ctx->sym_fwd, ctx->sym_fwd, 0, nullptr, 0.0, states, st, &per);
+    if (rc) return rc;
+    rc = dct2d_launch_sym(ctx, *w1, *w0, planes, ctx->sym_inv, ctx->sym_inv, 1, nullptr, 0.0, states, st);
+    std::swap(*w0, *w1);
+    return rc;
+  }
+  int rc = dct2d_launch(ctx, *w0, *w1, planes, 0, states, st);
+  if (rc) return rc;
+  rc = rep_apply_launch(ctx, per, p->ldm, *w1, *w0, p->d, p->m, states, st);
+  return rc ? rc : dct2d_launch(ctx, *w0, *w1, planes, 1, states, st);
 }
 
 // Masked blur (op = 5: the fields of op 1, op = 6: those of op 4, both with per.mask): A = M B, so
@@ -3359,31 +3464,27 @@ static int colorize_prepare(fh_context* ctx, const fh_problem* p, const fh_batch
 // Op 13 is op 12 in the same way: the adjoint frame kernels read uin = W u, and the forward ones finish with the weights
 // (frames_launch: the WEIGHTED epilogue of the fused kernel, or k_mask per frame on the chain) - the same expression, so
 // the two routes agree bit for bit, all-ones weights with sigma_y^2 = s^2 give op 12 and K = 1 gives op 10.
+// (amm_prologue has checked p and per for the entry point that calls this)
 static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per, const double* u, double* out,
                       const fh_cg_state* states, hipStream_t st, double* dot_part = nullptr, int* dot_nparts = nullptr,
                       const double* uin = nullptr) {
   if (uin == nullptr) uin = u;
   if (dot_nparts != nullptr) *dot_nparts = 0;
   static const bool no_dot_fuse = getenv("FH_CG_NO_DOT_FUSE") != nullptr;  // A/B switch
-  if (no_dot_fuse) dot_part = nullptr;
-  const int S = ctx->S;
+  const op_facts& f = facts(p);
+  if (no_dot_fuse || !f.dot_partials) dot_part = nullptr;
+  const int S = ctx->S, nimg = per.nimg, planes = p->planes * nimg;
   const int64_t d = p->d;  // per image
-  const int nimg = per.nimg;
-  const int planes = p->planes * nimg;
   if (d != (int64_t)p->planes * S * S || p->planes != 3 || nimg < 1 || nimg > ctx->nimg_max) return FH_EINVAL;
-  int rc = problem_check(p, S);
-  if (rc) return rc;
-  rc = masks_check(p, per);
-  if (rc) return rc;
-  const bool blur = p->op == 1 || p->op == 5 || p->op == 8, window = p->op == 4 || p->op == 6 || p->op == 9;
-  const fh_batch* masks = masked_op(p) || weighted_op(p) ? &per : nullptr;
+  int rc;
+  const fh_batch* masks = f.mask == MASK_VALID || f.mask == MASK_WEIGHTS_WP ? &per : nullptr;
   fh_batch mdiag;  // the masks as the per-image table of k_dct_sym's epilogue (indexed by the natural output pixel)
   memset(&mdiag, 0, sizeof(mdiag));
   mdiag.nimg = nimg;
   for (int i = 0; masks != nullptr && i < nimg; ++i) mdiag.D[i] = per.mask[i];
   const fh_batch* mtab = masks != nullptr ? &mdiag : nullptr;
   double *w0 = ctx->w0, *w1 = ctx->w1;
-  if (p->op == 3) {
+  if (f.apply == APPLY_MIX) {
     // colorization: u, out are ONE plane per image, A = channel mix with the three weights in tap_w.  The 2-D DCT acts per
     // plane, so it commutes with the mix: A C A^T u = idct2( sum_c w_c (C_dct (w_c dct2(u)))_c ) - one forward and one
     // inverse DCT over nimg planes instead of 3 nimg
@@ -3423,69 +3524,36 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
                        0.0, states);
     return dct2d_launch(ctx, w0, out, nimg, 1, states, st, 1, u, p->sigma_y2, dot_part, kCgScratch, dot_nparts);
   }
-  if (p->op == 7 || p->op == 11) {
+  if (f.apply == APPLY_RECT) {
     // rank-1 PSF + decimation folded into rectangular DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in four small
-    // dense passes + the apply; u, out are [3][So][So] per image.  With no factor columns C z = D .* z rides in forward pass B.
+    // dense passes + the apply; u, out are [3][So][So] per image.
     // op 11: the first pass reads uin = W u, and inverse pass B carries the weights as its table, out = fma(sigma_y^2, u, w * t)
-    const int So = S / p->stride;
-    if (planes > ctx->planes_max) return FH_ESIZE;
-    if (p->m == 0) {
-      rc = dct_rect_launch(ctx, uin, w0, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st, &per);
-      if (rc) return rc;
-    } else {
-      rc = dct_rect_launch(ctx, uin, w1, planes, p->fold_fwd_w, p->fold_fwd_h, So, 0, nullptr, 0.0, states, st);
-      if (rc) return rc;
-      rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
-      if (rc) return rc;
-    }
-    return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, So, 1, u, p->sigma_y2, states, st, mtab,
+    rc = cov_in_dct_launch(ctx, p, per, uin, false, states, st);
+    if (rc) return rc;
+    return dct_rect_launch(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, S / p->stride, 1, u, p->sigma_y2, states, st, mtab,
                            dot_part, kCgScratch, dot_nparts);
   }
-  if (hartley_op(p)) {
+  if (f.apply == APPLY_HARTLEY) {
     // Fourier sampling, A0 = H = R o (Hc . Hc) with Hc folded into the DCT bases (P = C_dct Hc, or Hc itself on the identity
     // basis):  out = sigma_y^2 u + W R( P^T (C (P R(W u) P^T)) P ).  The head butterfly reads u and the weights itself (uin is
     // not used: the CG keeps no W p vector for this op), the tail one finishes fma(sigma_y^2, u, w * R(t)) and the p.Ap partials.
-    if (planes > ctx->planes_max) return FH_ESIZE;
-    if (!aligned16(u, out) || u == out) return FH_EINVAL;  // 16-byte accesses; the tail butterfly reads u while it writes out
-    for (int i = 0; i < nimg; ++i)
-      if (!aligned16(per.mask[i])) return FH_EINVAL;
+    // (16-byte accesses, and the tail butterfly reads u while it writes out: amm_prologue has refused other operands)
     rc = hartley_launch(ctx, u, w1, planes, &per, nullptr, 0, nullptr, 0.0, states, st);
     if (rc) return rc;
-    if (p->m == 0) {
-      rc = dct_rect_launch(ctx, w1, w0, planes, p->fold_fwd_w, p->fold_fwd_h, S, 0, nullptr, 0.0, states, st, &per);
-      if (rc) return rc;
-    } else {
-      rc = dct_rect_launch(ctx, w1, w1, planes, p->fold_fwd_w, p->fold_fwd_h, S, 0, nullptr, 0.0, states, st);
-      if (rc) return rc;
-      rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
-      if (rc) return rc;
-    }
+    rc = cov_in_dct_launch(ctx, p, per, w1, false, states, st);
+    if (rc) return rc;
     rc = dct_rect_launch(ctx, w0, w1, planes, p->fold_inv_w, p->fold_inv_h, S, 1, nullptr, 0.0, states, st);
     if (rc) return rc;
     return hartley_launch(ctx, w1, out, planes, nullptr, &per, 0, u, p->sigma_y2, states, st, dot_part, kCgScratch, dot_nparts);
   }
-  const int halo = p->halo;
-  const dim3 egrid(512, 1, (unsigned)nimg);
-  const bool frames = frames_op(p);               // multi-frame SR: ntaps2 counts frames, tap2_dy holds their offsets
-  const bool blend = blend_op(p);                 // varying blur: the same two fields, and the maps in tap2_w
-  const bool sep = !frames && !blend && p->ntaps2 > 0;  // separable PSF: two 1-D passes (blur only, stride 1)
-  if (sep && p->stride != 1) return FH_EINVAL;
-  if (blur && p->use_dct && p->fold_fwd_w != nullptr) {
+  // a second tap list outside ops 12 .. 14 (which count frames there) is the other factor of a separable PSF: stride 1 only
+  if (f.apply != APPLY_FRAMES && f.apply != APPLY_BLEND && p->ntaps2 > 0 && p->stride != 1) return FH_EINVAL;
+  if (f.foldable && p->use_dct && p->fold_fwd_w != nullptr) {
     // separable blur folded into the DCT bases: out = sigma_y^2 u + A idct2( C dct2(A^T u) ) in 4 dense passes + the
     // apply, instead of 4 blur passes + 4 DCT passes + the apply + an axpy epilogue
     if (!p->fold_fwd_h || !p->fold_inv_w || !p->fold_inv_h) return FH_EINVAL;
     if (p->fold_sym) {  // symmetric PSF: the fold pointers are packed half bases (k_dct_sym)
-      if (p->m == 0) {
-        // no factor columns yet (every call above sigma = 10, i.e. three quarters of all CG iterations of a Heun-30 run): C z =
-        // D .* z rides in the epilogue of the forward pass - two kernels per apply instead of three
-        rc = dct2d_launch_sym(ctx, uin, w0, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st, &per);
-        if (rc) return rc;
-        return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, mtab,
-                                dot_part, kCgScratch, dot_nparts);
-      }
-      rc = dct2d_launch_sym(ctx, uin, w1, planes, p->fold_fwd_w, p->fold_fwd_h, 0, nullptr, 0.0, states, st);
-      if (rc) return rc;
-      rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
+      rc = cov_in_dct_launch(ctx, p, per, uin, true, states, st);
       if (rc) return rc;
       return dct2d_launch_sym(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, 1, u, p->sigma_y2, states, st, mtab,
                               dot_part, kCgScratch, dot_nparts);
@@ -3494,86 +3562,73 @@ static int amm_launch(fh_context* ctx, const fh_problem* p, const fh_batch& per,
     if (rc) return rc;
     rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
     if (rc) return rc;
-    if (masks != nullptr) {  // k_gemm_f64 has no masked epilogue: B w to w1, then out = sigma_y^2 u + mask .* w1
-      rc = dct2d_launch_bases(ctx, w0, w1, planes, p->fold_inv_w, p->fold_inv_h, nullptr, 0.0, states, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out,
-                         d, states);
-      FH_LAUNCH_CHECK();
-      return 0;
+    if (masks == nullptr) return dct2d_launch_bases(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, u, p->sigma_y2, states, st);
+    // k_gemm_f64 has no masked epilogue: B w to w1, then out = sigma_y^2 u + mask .* w1
+    rc = dct2d_launch_bases(ctx, w0, w1, planes, p->fold_inv_w, p->fold_inv_h, nullptr, 0.0, states, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out, d, states);
+    FH_LAUNCH_CHECK();
+    return 0;
+  }
+  // w0 = A^T u  (w1 is free until the covariance apply: the spare)
+  rc = op_apply_launch(ctx, p, per, 1, uin, w0, w1, nullptr, 0.0, nullptr, states, st);
+  if (rc) return rc;
+  // w1 = C w0  (the two may have swapped)
+  rc = cov_apply_launch(ctx, p, per, &w0, &w1, states, st);
+  if (rc) return rc;
+  // out = sigma_y^2 u + A w1  (w0 has been read: the spare)
+  return op_apply_launch(ctx, p, per, 0, w1, out, w0, u, p->sigma_y2, masks, states, st);
+}
+
+// What fh_amm and fh_cg_solve_batched do once, before the first apply: every refusal that needs no launch, D_eff of the
+// colorization route, the host copy of the frame offsets, the CG's W p vector, and the input side of the first apply.
+// in / io: the entry point's measurement-space operands (u / out, b / x).  *n: the measurement's length per image.
+// *uin: null, or `in` times the op's mask / weights (amm_launch: the input-side M or W), left in a CG vector.
+enum amm_entry { ENTRY_AMM, ENTRY_SOLVE };  // where the two have always answered differently, each keeps its answer
+static int amm_prologue(fh_context* ctx, const fh_problem* p, const fh_batch& per, amm_entry entry, const double* in,
+                        const double* io, hipStream_t st, int64_t* n, const double** uin) {
+  const int S = ctx->S, nimg = per.nimg;
+  *uin = nullptr;
+  if (problem_check(p, S) || masks_check(p, per)) return FH_EINVAL;
+  const op_facts& f = facts(p);
+  if (f.decimated && p->stride < 1) return FH_EINVAL;  // (op 2, whose stride problem_check leaves to conv_plan)
+  const int So = S / (f.decimated ? p->stride : 1);
+  // per image: one plane for colorization, 3 K for the K frames of ops 12 / 13, else 3
+  *n = (int64_t)(f.meas == MEAS_ONE_PLANE ? 1 : (f.meas == MEAS_PER_FRAME ? p->ntaps2 : 1) * p->planes) * So * So;
+  const bool maps = f.mask == MASK_VALID || f.mask == MASK_WEIGHTS_WP || f.mask == MASK_WEIGHTS_SELF;
+  if (maps || f.graph_route != nullptr) {  // sizes, before the offsets are read and before the first launch
+    if (p->planes != 3 || p->d != (int64_t)3 * S * S) return FH_EINVAL;
+    if (entry == ENTRY_SOLVE && *n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;  // the CG vectors hold the batch
+    if (entry == ENTRY_AMM && maps && ctx->planes_max < 3) return FH_ESIZE;
+  }
+  if (f.align16 && !aligned16(in, io)) return FH_EINVAL;  // k_channel_mix, k_hartley_fix: 16-byte accesses
+  const bool self = f.mask == MASK_WEIGHTS_SELF;
+  if (self && entry == ENTRY_AMM && in == io) return FH_EINVAL;  // the tail butterfly reads u while it writes out
+  for (int i = 0; self && i < nimg; ++i)  // (the weights: masks_check found them non-null)
+    if (!aligned16(per.mask[i])) return FH_EINVAL;
+  int rc = colorize_prepare(ctx, p, per, st);
+  if (rc) return rc;
+  int total = p->ntaps;  // the offsets, read and checked once (the chain route launches from the host copy)
+  rc = f.graph_route != nullptr ? frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, st) : 0;
+  if (rc) return rc;
+  if (f.mask != MASK_VALID && f.mask != MASK_WEIGHTS_WP) return 0;
+  // The input-side mask / weights of the first apply (amm_launch: uin), one k_mask pass into a CG vector.  fh_amm: cg_p (idle).
+  // Solve of a masked blur: the system is solved for M b - the one masking of a solve; the iteration then needs no input-side
+  // mask.  M b goes to cg_x for the first apply (and, once that has released the work vectors, to w0 for k_cg_init).
+  // Solve with a noise map: b is the caller's whitened right-hand side and is solved for as given.  W p of every iteration
+  // lives in one more CG vector, allocated by the first such solve of this context (under the capture lock, as
+  // colorize_prepare's scratch; never inside a capture); W b for the x0 = b apply goes there (cg_scipy: x0 = 0, no such apply).
+  if (entry == ENTRY_SOLVE && f.mask == MASK_WEIGHTS_WP) {
+    if (ctx->cg_wp == nullptr) {
+      std::lock_guard<std::mutex> capture_lock(g_capture_mu);
+      FH_CHECK(hipMalloc(&ctx->cg_wp, sizeof(double) * ctx->nimg_max * 3 * S * S));
     }
-    return dct2d_launch_bases(ctx, w0, out, planes, p->fold_inv_w, p->fold_inv_h, u, p->sigma_y2, states, st);
+    if (p->cg_scipy) return 0;
   }
-  // w0 = A^T u
-  if (p->op == 0) {
-    hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, u, (const double*)nullptr, 0.0, w0, d, states);
-  } else if (window) {
-    rc = window_launch(ctx, uin, w0, p->tap_w, halo / 64, halo % 64, planes, 1, nullptr, 0.0, states, st);
-    if (rc) return rc;
-  } else if (frames) {
-    rc = frames_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
-                       p->stride, 1, nullptr, 0.0, states, st);
-    if (rc) return rc;
-  } else if (blend) {
-    rc = blend_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes, 1,
-                      p->tap2_w, nullptr, 0.0, states, st, w1);  // (w1 is free until the covariance apply: the chain's spare)
-    if (rc) return rc;
-  } else if (sep) {
-    rc = conv_launch(ctx, uin, w1, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 1, nullptr, 0.0,
-                     states, st);
-    if (rc) return rc;
-    rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 1, nullptr, 0.0, states, st);
-    if (rc) return rc;
-  } else {
-    rc = conv_launch(ctx, uin, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, 1, nullptr, 0.0,
-                     states, st);
-    if (rc) return rc;
-  }
-  // w0 <- C w0  (through the DCT basis when the covariance lives there)
-  if (p->use_dct && p->m == 0 && sym_dct(ctx)) {
-    // as above: the diagonal-only covariance apply inside the forward DCT's second pass
-    rc = dct2d_launch_sym(ctx, w0, w1, planes, ctx->sym_fwd, ctx->sym_fwd, 0, nullptr, 0.0, states, st, &per);
-    if (rc) return rc;
-    rc = dct2d_launch_sym(ctx, w1, w0, planes, ctx->sym_inv, ctx->sym_inv, 1, nullptr, 0.0, states, st);
-    if (rc) return rc;
-    { double* t_ = w0; w0 = w1; w1 = t_; }  // the result is expected in w1 below
-  } else if (p->use_dct) {
-    rc = dct2d_launch(ctx, w0, w1, planes, 0, states, st);
-    if (rc) return rc;
-    rc = rep_apply_launch(ctx, per, p->ldm, w1, w0, d, p->m, states, st);
-    if (rc) return rc;
-    rc = dct2d_launch(ctx, w0, w1, planes, 1, states, st);
-    if (rc) return rc;
-  } else {
-    rc = rep_apply_launch(ctx, per, p->ldm, w0, w1, d, p->m, states, st);
-    if (rc) return rc;
-  }
-  // out = sigma_y^2 u + A w1
-  if (p->op == 0) {
-    hipLaunchKernelGGL(k_mask, egrid, dim3(256), 0, st, per, (const double*)w1, u, p->sigma_y2, out, d, states);
-  } else if (window) {
-    rc = window_launch(ctx, w1, out, p->tap_w, halo / 64, halo % 64, planes, 0, u, p->sigma_y2, states, st, masks);
-    if (rc) return rc;
-  } else if (frames) {
-    rc = frames_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes,
-                       p->stride, 0, u, p->sigma_y2, states, st, masks, w0);  // (op 13: w0 is the spare, as below)
-    if (rc) return rc;
-  } else if (blend) {
-    rc = blend_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->tap2_dy, p->ntaps, p->ntaps2, p->halo2, halo, planes, 0,
-                      p->tap2_w, u, p->sigma_y2, states, st, w0);  // (w0 has been read: the chain's spare)
-    if (rc) return rc;
-  } else if (sep) {
-    rc = conv_launch(ctx, w1, w0, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, 1, 0, nullptr, 0.0, states, st);
-    if (rc) return rc;
-    rc = conv_launch(ctx, w0, out, p->tap2_dy, p->tap2_dx, p->tap2_w, p->ntaps2, p->halo2, planes, 1, 0, u, p->sigma_y2,
-                     states, st, masks, w1);  // (w1 has been read: it is the spare of a pass without a masked epilogue)
-    if (rc) return rc;
-  } else {
-    rc = conv_launch(ctx, w1, out, p->tap_dy, p->tap_dx, p->tap_w, p->ntaps, halo, planes, p->stride, 0, u, p->sigma_y2,
-                     states, st, masks, w0);
-    if (rc) return rc;
-  }
-  FH_LAUNCH_CHECK();
+  double* dst = entry == ENTRY_AMM ? ctx->cg_p : (f.mask == MASK_VALID ? ctx->cg_x : ctx->cg_wp);
+  hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, in, (const double*)nullptr, 0.0, dst, *n,
+                     (const fh_cg_state*)nullptr);
+  *uin = dst;
   return 0;
 }
 
@@ -4483,28 +4538,12 @@ int fh_channel_mix(fh_context* ctx, const double* in, double* out, const double*
 
 int fh_amm(fh_context* ctx, const fh_problem* p, const double* u, double* out, void* stream) {
   if (!ctx || !p || !u || !out) return FH_EINVAL;
-  if (problem_check(p, ctx->S)) return FH_EINVAL;
-  if (p->op == 3 && (((uintptr_t)u | (uintptr_t)out) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
   const fh_batch per = batch_of(p);
-  if (masks_check(p, per)) return FH_EINVAL;
-  const int rc = colorize_prepare(ctx, p, per, (hipStream_t)stream);
+  int64_t n;          // (the measurement's length: not needed here)
+  const double* uin;  // u times the op's mask / weights, or null
+  const int rc = amm_prologue(ctx, p, per, ENTRY_AMM, u, out, (hipStream_t)stream, &n, &uin);
   if (rc) return rc;
-  if (frames_op(p) || blend_op(p)) {  // (before the first launch of op 13 as well)
-    if (blend_op(p) && (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3)) return FH_EINVAL;
-    int total = p->ntaps;
-    const int rcf = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, (hipStream_t)stream);
-    if (rcf) return rcf;
-  }
-  if (masked_op(p) || weighted_op(p)) {
-    // the input-side mask / weights of A_mm (amm_launch): M u or W u into a CG vector, which is idle outside a solve
-    if (p->d != (int64_t)3 * ctx->S * ctx->S || p->planes != 3) return FH_EINVAL;
-    if (ctx->planes_max < 3) return FH_ESIZE;
-    const int So = ctx->S / (decimating_op(p) ? p->stride : 1);
-    hipLaunchKernelGGL(k_mask, dim3(512, 1, 1), dim3(256), 0, (hipStream_t)stream, per, u, (const double*)nullptr, 0.0, ctx->cg_p,
-                       (int64_t)meas_planes(p) * So * So, (const fh_cg_state*)nullptr);
-    return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, ctx->cg_p);
-  }
-  return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream);
+  return amm_launch(ctx, p, per, u, out, nullptr, (hipStream_t)stream, nullptr, nullptr, uin);
 }
 
 // One chunk of CG iterations for all images of the batch, enqueued on `st` (eagerly, or while the stream is being
@@ -4516,7 +4555,7 @@ static int cg_enqueue_chunk(fh_context* ctx, const fh_problem* p, const fh_batch
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;
   fh_cg_state* stt = ctx->cg_state;
   const dim3 grid(kCgBlocks, 1, (unsigned)per.nimg);
-  const bool weighted = weighted_op(p);  // the operator reads W p, which k_cg_step2_w leaves in cg_wp beside p
+  const bool weighted = cg_keeps_wp(p);  // the operator reads W p, which k_cg_step2_w leaves in cg_wp beside p
   const fh_diag_tab wt = weights_tab(per);
   for (int i = 0; i < count; ++i) {
     int dot_n = 0;  // > 0: the operator's last pass already left the p.Ap block partials
@@ -4549,8 +4588,9 @@ static hipGraphExec_t cg_graph_for(fh_context* ctx, const fh_problem* p, const f
   // ops 12 / 13: the chain route bakes host-sliced tap pointers and counts into the graph, so the route switch and the offsets
   // that frames_prepare has just checked (ctx->frame_off) belong to the key; other ops never read the switch.  (The weights'
   // pointers of op 13 are part of bkey, like those of ops 8 .. 11; their values are read by the kernels at every replay.)
-  const bool offsets_op = frames_op(p) || blend_op(p);  // op 14: the same, with its own switch (FH_BLEND_FUSED)
-  const int frames_route = frames_op(p) ? (int)frames_fused_on() : (blend_op(p) ? (int)blend_fused_on() : 0);
+  bool (*const route)() = facts(p).graph_route;  // op 14: the same, with its own switch (FH_BLEND_FUSED)
+  const bool offsets_op = route != nullptr;
+  const int frames_route = offsets_op ? (int)route() : 0;
   fh_graph_entry* slot = &ctx->graphs[0];
   for (auto& g : ctx->graphs) {
     if (g.exec != nullptr && g.n == n && memcmp(&g.key, p, sizeof(fh_problem)) == 0 &&
@@ -4610,72 +4650,31 @@ int fh_cg_solve_batched(fh_context* ctx, const fh_problem* p, const fh_batch* pe
   const int nimg = per.nimg;
   if (nimg < 1 || nimg > ctx->nimg_max || nimg > FH_MAX_BATCH) return FH_ESIZE;
   hipStream_t st = (hipStream_t)stream;
-  const int S = ctx->S;
-  if (problem_check(p, S) || masks_check(p, per) || (p->op == 2 && p->stride < 1)) return FH_EINVAL;
-  if (p->op == 3 && (((uintptr_t)b | (uintptr_t)x) & 15)) return FH_EINVAL;  // k_channel_mix: 16-byte accesses
-  const int So = S / (decimating_op(p) ? p->stride : 1);
-  const int64_t n = (int64_t)meas_planes(p) * So * So;  // per image (colorization: one plane, ops 12 / 13: 3 K)
+  for (int i = 0; i < nimg; ++i)
+    if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
+  int64_t n;  // per image (colorization: one plane, ops 12 / 13: 3 K)
+  const double* uin;
+  int rc = amm_prologue(ctx, p, per, ENTRY_SOLVE, b, x, st, &n, &uin);
+  if (rc) return rc;
   double *r = ctx->cg_r, *pk = ctx->cg_p, *ap = ctx->cg_ap;
   double* part = ctx->w2;                      // per image: [0,256) pAp / init r.r ; [256,512) init b.b ; [512,768) r.r
   double* rzbuf = ctx->w2 + 4 * kDotBlocks;    // per image: [2]
   fh_cg_state* stt = ctx->cg_state;
   RtolArr rt;
   for (int i = 0; i < FH_MAX_BATCH; ++i) rt.v[i] = i < nimg ? rtol_host[i] : 1.0;
-  for (int i = 0; i < nimg; ++i)
-    if (!(rtol_host[i] > 0 || atol > 0)) return FH_EINVAL;
-  int rc = colorize_prepare(ctx, p, per, st);
-  if (rc) return rc;
-  if (frames_op(p) || blend_op(p)) {  // the offsets, read and checked once per solve (the chain route launches from the host copy)
-    if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
-    int total = p->ntaps;
-    rc = frames_prepare(ctx, p->tap2_dy, p->ntaps2, &total, p->halo2, st);
+  const bool masked = facts(p).mask == MASK_VALID;  // the system is solved for M b, which amm_prologue has left in cg_x
+  if (!p->cg_scipy) {  // A x0 with x0 = b
+    rc = masked ? amm_launch(ctx, p, per, uin, ap, nullptr, st)
+                : amm_launch(ctx, p, per, b, ap, nullptr, st, nullptr, nullptr, uin);
     if (rc) return rc;
   }
-  if (masked_op(p)) {
-    // masked blur: the system is solved for M b - the one masking of a solve; the iteration then needs no input-side mask
-    // (amm_launch).  M b goes to cg_x for the first apply and, once that has released the work vectors, to w0 for k_cg_init
-    if (p->d != n || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
-    const dim3 mgrid(512, 1, (unsigned)nimg);
-    hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->cg_x, n,
-                       (const fh_cg_state*)nullptr);
-    if (!p->cg_scipy) {
-      rc = amm_launch(ctx, p, per, ctx->cg_x, ap, nullptr, st);
-      if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_mask, mgrid, dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->w0, n,
+  if (masked) {  // (the first apply has released the work vectors)
+    hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->w0, n,
                        (const fh_cg_state*)nullptr);
     b = ctx->w0;
-  } else if (weighted_op(p)) {
-    // noise map: b is the caller's whitened right-hand side and is solved for as given.  W p of every iteration lives in one
-    // more CG vector, allocated by the first such solve of this context (under the capture lock, as colorize_prepare's
-    // scratch; never inside a capture); W b for the x0 = b apply comes from one k_mask pass
-    if (p->planes != 3 || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
-    if (ctx->cg_wp == nullptr) {
-      std::lock_guard<std::mutex> capture_lock(g_capture_mu);
-      FH_CHECK(hipMalloc(&ctx->cg_wp, sizeof(double) * ctx->nimg_max * 3 * S * S));
-    }
-    if (!p->cg_scipy) {
-      hipLaunchKernelGGL(k_mask, dim3(512, 1, (unsigned)nimg), dim3(256), 0, st, per, b, (const double*)nullptr, 0.0, ctx->cg_wp,
-                         n, (const fh_cg_state*)nullptr);
-      rc = amm_launch(ctx, p, per, b, ap, nullptr, st, nullptr, nullptr, ctx->cg_wp);
-      if (rc) return rc;
-    }
-  } else if (hartley_op(p)) {
-    // Fourier sampling: sizes and alignment are refused here, before k_cg_init - with cg_scipy no apply precedes it
-    if (p->planes != 3 || p->d != n || n * nimg > (int64_t)ctx->planes_max * S * S) return FH_EINVAL;
-    if (!aligned16(b, x)) return FH_EINVAL;  // 16-byte accesses (the weights: masks_check found them non-null)
-    for (int i = 0; i < nimg; ++i)
-      if (!aligned16(per.mask[i])) return FH_EINVAL;
-    if (!p->cg_scipy) {
-      rc = amm_launch(ctx, p, per, b, ap, nullptr, st);
-      if (rc) return rc;
-    }
-  } else if (!p->cg_scipy) {
-    rc = amm_launch(ctx, p, per, b, ap, nullptr, st);  // A x0 with x0 = b
-    if (rc) return rc;
   }
   const dim3 grid(kCgBlocks, 1, (unsigned)nimg);
-  if (weighted_op(p))
+  if (cg_keeps_wp(p))
     hipLaunchKernelGGL(k_cg_init_w, grid, dim3(256), 0, st, b, p->cg_scipy ? (const double*)nullptr : (const double*)ap,
                        ctx->cg_x, r, pk, part, n, weights_tab(per), ctx->cg_wp);
   else
