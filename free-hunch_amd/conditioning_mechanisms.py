@@ -16,6 +16,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from typing import NamedTuple
 from warnings import warn
 
 import numpy as np
@@ -62,43 +63,66 @@ def rtol_func(sigma, rtol_max=1e0, rtol_min=1e-14):
     return 10 ** (frac * (math.log10(rtol_max) - math.log10(rtol_min)) + math.log10(rtol_min))
 
 
-# fh_problem.op (include/fh_hip.h); denoising (A = I) is inpainting with an all-ones mask
-# (a custom_blur whose PSF runs on the dense-window kernel is op = 4, a masked_blur's op = 6, a custom_sr whose rank-1 PSF folds
-# into rectangular DCT bases op = 7, see _problem; a weighted_blur on the dense-window kernel is op = 9, a weighted_sr on the
-# rectangular bases op = 11; burst_sr is op = 12, the multi-frame operator pair of fh_conv_frames, and weighted_burst_sr is
-# op = 13, the same pair with a noise map on the burst; varying_blur is op = 14, the blended PSFs of fh_conv_blend;
-# fourier_sampling, op = 15, lives in _OP_CODE_MORE below: look names up with _op_code)
-_OP_CODE = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
-            "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10,
-            "burst_sr": 12, "weighted_burst_sr": 13, "varying_blur": 14}
-# operators added after the table above was pinned by the tests; fourier_sampling is op = 15, measurement in the Hartley domain
-# (fh_hartley2d) with the sampling mask or the 1 / sigma map as the solver's weights
-_OP_CODE_MORE = {"fourier_sampling": 15}
-_MASKED = ("inpainting", "noise")  # operators whose A is a 0/1 mask
-# operators whose PSF is the caller's: a lock-step batch must share it
-_SHARED_PSF = ("custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr")
-# operators with a scale_factor: A = blur + decimation on the PSF's tap list
-_DECIMATING = ("super_resolution", "custom_sr", "weighted_sr", "burst_sr", "weighted_burst_sr")
-# operators with a per-pixel noise map: the solver whitens with operator.weights = 1 / sigma_i and sigma_y2 = 1 (ops 8 .. 11, 13)
-_WEIGHTED = ("weighted_blur", "weighted_sr", "weighted_burst_sr")
-# operators on K frames with one PSF each: A is the operator pair of fh_conv_frames, the measurement [3 K, So, So] per image
-_BURST = ("burst_sr", "weighted_burst_sr")
-# Fourier-domain measurement: whitened like _WEIGHTED through operator.weights, which is the 0/1 mask (sigma_y2 from sigma_s)
-# or 1 / sigma of a noise map (sigma_y2 = 1)
-_FOURIER = ("fourier_sampling",)
-_BAD_OPERATOR = ("Invalid operator name. Please choose 'gaussian_blur', 'super_resolution', 'motion_blur', 'inpainting', "
-                 "'colorization', 'noise', 'custom_blur', 'masked_blur', 'custom_sr', 'weighted_blur', or 'weighted_sr'. Also 'burst_sr' and "
-                 "'weighted_burst_sr'. Also 'fourier_sampling'. Also 'varying_blur'.")
+class _Row(NamedTuple):
+    """What the solver side knows of an operator name; the library's side of the same is kOps[fh_problem.op]."""
+    op: int                   # fh_problem.op (include/fh_hip.h)
+    layout: str               # the fields `_problem` fills (kOps[].apply): mask, mix, taps, frames, blend, hartley; "mask" is also the
+    #                           masked form of b and mat (M y - M x0, mat = u), every other layout forms them with operator.apply
+    window: int = None        # the op when the PSF runs as a dense window (`Taps.window`): 1 -> 4, 5 -> 6, 8 -> 9
+    rect: int = None          # the op when a rank-1 PSF folds into rectangular DCT bases (`folded_sr_bases`): 2 -> 7, 10 -> 11
+    decimating: bool = False  # stride = operator.scale_factor, and `_sigma_y2` also clips sigma_s at 1e-2
+    rides: str = None         # the operator's attribute in fh_problem.mask, last in `keep`: "mask" (0/1 validity, multiplies b) or
+    #                           "weights" (they whiten the system: b = W (y - A0 x0), mat = A0^T W u)
+    unit_sigma: str = None    # sigma_y2 = 1 instead of `_sigma_y2`: "always", or "noise_map" = when the operator carries one
+    shares: tuple = ()        # what a lock-step batch must share, keys of `_SHARED` in the order they are checked
+
+
+def _same_psfs(op, op0, S):
+    return op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(op.kernels, op0.kernels))
+
+
+# "lock-step images must ..." -> the test of an image's operator against the batch's first (S: the covariance's image side)
+_SHARED = {
+    "share the channel weights": lambda op, op0, S: op.channel_weights == op0.channel_weights,
+    "share the PSF": lambda op, op0, S: torch.equal(op.taps.kernel, op0.taps.kernel),
+    "share the PSF of every frame": _same_psfs,
+    "share every PSF": _same_psfs,
+    "share the blend maps": lambda op, op0, S: op.blend.shape == op0.blend.shape and torch.equal(op.blend, op0.blend),
+    "share the scale_factor": lambda op, op0, S: op.scale_factor == op0.scale_factor,
+    "share the image side": lambda op, op0, S: op.in_shape[-1] == S and op0.in_shape[-1] == S,
+    "all carry a noise map or share the noise level":
+        lambda op, op0, S: (op.noise_map is None) == (op0.noise_map is None) and _solver_sigma_y2(op) == _solver_sigma_y2(op0),
+}
+_PSF, _FACTOR = "share the PSF", "share the scale_factor"
+
+# One row per operator name, in the order `_BAD_OPERATOR` lists them.  Denoising (A = I) is inpainting with an all-ones mask.
+_OPS = {
+    "gaussian_blur": _Row(1, "taps", window=4),
+    "super_resolution": _Row(2, "taps", decimating=True),
+    "motion_blur": _Row(1, "taps", window=4),
+    "inpainting": _Row(0, "mask", rides="mask"),
+    "colorization": _Row(3, "mix", shares=("share the channel weights",)),
+    "noise": _Row(0, "mask", rides="mask"),
+    "custom_blur": _Row(1, "taps", window=4, shares=(_PSF,)),
+    "masked_blur": _Row(5, "taps", window=6, rides="mask", shares=(_PSF,)),
+    "custom_sr": _Row(2, "taps", rect=7, decimating=True, shares=(_PSF, _FACTOR)),
+    "weighted_blur": _Row(8, "taps", window=9, rides="weights", unit_sigma="always", shares=(_PSF,)),
+    "weighted_sr": _Row(10, "taps", rect=11, decimating=True, rides="weights", unit_sigma="always", shares=(_PSF, _FACTOR)),
+    "burst_sr": _Row(12, "frames", decimating=True, shares=("share the PSF of every frame", _FACTOR)),
+    "weighted_burst_sr": _Row(13, "frames", decimating=True, rides="weights", unit_sigma="always",
+                              shares=("share the PSF of every frame", _FACTOR)),
+    "fourier_sampling": _Row(15, "hartley", rides="weights", unit_sigma="noise_map",
+                             shares=("share the image side", "all carry a noise map or share the noise level")),
+    "varying_blur": _Row(14, "blend", shares=("share every PSF", "share the blend maps")),
+}
+_quoted = [f"'{name}'" for name in _OPS]
+_BAD_OPERATOR = ("Invalid operator name. Please choose " + ", ".join(_quoted[:10]) + f", or {_quoted[10]}. Also {_quoted[11]} and "
+                 f"{_quoted[12]}." + "".join(f" Also {q}." for q in _quoted[13:]))
 
 
 def _op_code(name):
     """fh_problem.op of an operator name, None for a name the solver does not know"""
-    return _OP_CODE.get(name, _OP_CODE_MORE.get(name))
-
-
-def _whitened(name):
-    """the solver multiplies operator.weights into the right-hand side and into the solution (W (y - A0 x0), A0^T W u)"""
-    return name in _WEIGHTED or name in _FOURIER
+    return getattr(_OPS.get(name), "op", None)
 
 
 def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
@@ -109,102 +133,146 @@ def rtol_func_2(sigma, rtol_max=1e0, rtol_min=1e-4):
     return 10 ** (frac * (math.log10(rtol_max) - math.log10(rtol_min)) + math.log10(rtol_min))
 
 
-def _problem(operator, cov, sigma_y2):
+def _set_taps(p, t, prefix="tap"):
+    """the five fields of one tap list: ntaps, halo, tap_dy, tap_dx, tap_w - or, with prefix "tap2", their second set"""
+    second = "2" if prefix == "tap2" else ""
+    setattr(p, "ntaps" + second, t.n)
+    setattr(p, "halo" + second, t.halo)
+    for f in ("dy", "dx", "w"):
+        setattr(p, f"{prefix}_{f}", getattr(t, f).data_ptr())
+
+
+def _fill_mix(p, keep, operator, cov, row):  # the three channel weights travel in tap_w (ntaps = 3)
+    w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
+    p.ntaps, p.tap_w = 3, w.data_ptr()
+    keep.append(w)
+
+
+def _fill_taps(p, keep, operator, cov, row):
+    t = operator.taps
+    if row.window is not None and t.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
+        win, hy, hx = t.window
+        p.op, p.ntaps, p.halo, p.tap_w = row.window, win.numel(), 64 * hy + hx, win.data_ptr()
+        keep.append(win)
+        return
+    if t.sep is not None and not row.decimating:  # a rank-1 PSF at full resolution: the column list, the row list second
+        t, t2 = t.sep
+        _set_taps(p, t2, "tap2")
+    _set_taps(p, t)
+    fold = operator.folded_bases() if (cov.use_dct and not row.decimating) else None
+    if fold is not None:  # separable blur absorbed by the DCT passes of A C A^T (measurements.folded_dct_blur_bases)
+        mats, sym = fold
+        p.fold_sym = int(sym)
+    else:  # rank-1 PSF + decimation absorbed by rectangular DCT bases (measurements.folded_dct_sr_bases)
+        mats = operator.folded_sr_bases() if (cov.use_dct and row.rect is not None) else None
+        if mats is not None:
+            p.op = row.rect
+    if mats is not None:
+        p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in mats)
+        keep.extend(mats)
+
+
+def _fill_frames(p, keep, operator, cov, row):
+    """ops 12 / 13: the frames' tap lists concatenated, their offsets in tap2_dy (include/fh_hip.h); op 14: the PSFs' tap lists
+    the same way and the blend maps [K, 3, S, S] in tap2_w"""
+    ft = operator.frame_taps
+    _set_taps(p, ft)
+    p.ntaps2, p.halo2, p.tap2_dy = ft.nframes, ft.max_taps, ft.off.data_ptr()
+    keep.extend([ft.dy, ft.dx, ft.w, ft.off])
+    if row.layout == "blend":
+        blend = operator.blend.to(device=cov.device, dtype=F64).contiguous()
+        p.tap2_w = blend.data_ptr()
+        keep.append(blend)
+
+
+def _fill_hartley(p, keep, operator, cov, row):  # op 15: P = C_dct Hc (or Hc) on both sides, no taps
+    P, Pt = operator.folded_hartley_bases(cov.use_dct, cov.device)
+    p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = P.data_ptr(), P.data_ptr(), Pt.data_ptr(), Pt.data_ptr()
+    keep.extend([P, Pt])
+
+
+_FILL = {"mix": _fill_mix, "taps": _fill_taps, "frames": _fill_frames, "blend": _fill_frames, "hartley": _fill_hartley}  # "mask": none
+
+
+class _System(NamedTuple):
+    problem: object  # the FhProblem
+    keep: list       # the tensors its pointers address, in the order the tests and tools index
+    rides: object    # the tensor in fh_problem.mask (the row's `rides`, on the covariance's device), None without one
+
+
+def _system(operator, cov, sigma_y2):
+    row = _OPS[operator.name]
     p = _lib.FhProblem()
-    p.op = _op_code(operator.name)
+    p.op = row.op
     p.use_dct = int(cov.use_dct)
     p.planes = 3
-    p.stride = int(operator.scale_factor) if operator.name in _DECIMATING else 1
+    p.stride = int(operator.scale_factor) if row.decimating else 1
     p.d = cov.data_dim
     p.sigma_y2 = sigma_y2
     m = cov.famC.m
     p.m, p.ldm = m, cov.C.M_dev.shape[1]
     p.D, p.r, p.B, p.M = (cov.C.D.data_ptr(), cov.C.r.data_ptr(), cov.famC.B.data_ptr(), cov.C.M_dev.data_ptr())
     keep = [cov.C.D, cov.C.r, cov.famC.B, cov.C.M_dev]
-    if operator.name in _MASKED:
-        mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
-        p.mask = mask.data_ptr()
-        keep.append(mask)
-        return p, keep
-    if operator.name in _BURST:  # ops 12 / 13: the frames' tap lists concatenated, their offsets in tap2_dy (include/fh_hip.h)
-        ft = operator.frame_taps
-        p.ntaps, p.halo = ft.n, ft.halo
-        p.tap_dy, p.tap_dx, p.tap_w = ft.dy.data_ptr(), ft.dx.data_ptr(), ft.w.data_ptr()
-        p.ntaps2, p.halo2, p.tap2_dy = ft.nframes, ft.max_taps, ft.off.data_ptr()
-        keep.extend([ft.dy, ft.dx, ft.w, ft.off])
-        if operator.name in _WEIGHTED:  # op 13: the weights [3 K, So, So], frame-major like the measurement; kept LAST in `keep`
-            w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
-            p.mask = w.data_ptr()
-            keep.append(w)
-        return p, keep
-    if operator.name == "varying_blur":  # op 14: the PSFs' tap lists as for the frames, the blend maps [K, 3, S, S] in tap2_w
-        ft = operator.frame_taps
-        blend = operator.blend.to(device=cov.device, dtype=F64).contiguous()
-        p.ntaps, p.halo = ft.n, ft.halo
-        p.tap_dy, p.tap_dx, p.tap_w = ft.dy.data_ptr(), ft.dx.data_ptr(), ft.w.data_ptr()
-        p.ntaps2, p.halo2, p.tap2_dy, p.tap2_w = ft.nframes, ft.max_taps, ft.off.data_ptr(), blend.data_ptr()
-        keep.extend([ft.dy, ft.dx, ft.w, ft.off, blend])
-        return p, keep
-    if operator.name in _FOURIER:  # op 15: P = C_dct Hc (or Hc) on both sides, no taps; the weights kept LAST in `keep`
-        P, Pt = operator.folded_hartley_bases(cov.use_dct, cov.device)
-        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
-        p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = P.data_ptr(), P.data_ptr(), Pt.data_ptr(), Pt.data_ptr()
-        p.mask = w.data_ptr()
-        keep.extend([P, Pt, w])
-        return p, keep
-    if operator.name == "colorization":  # the three channel weights travel in tap_w (ntaps = 3)
-        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
-        p.ntaps, p.tap_w = 3, w.data_ptr()
-        keep.append(w)
-    elif p.op in (1, 5, 8) and operator.taps.window is not None:  # dense-window blur: the window travels in tap_w, its extents in halo
-        win, hy, hx = operator.taps.window
-        p.op, p.ntaps, p.halo, p.tap_w = {1: 4, 5: 6, 8: 9}[p.op], win.numel(), 64 * hy + hx, win.data_ptr()
-        keep.append(win)
-    else:
-        t = operator.taps
-        if t.sep is not None and operator.name not in _DECIMATING:
-            t, t2 = t.sep
-            p.ntaps2, p.halo2 = t2.n, t2.halo
-            p.tap2_dy, p.tap2_dx, p.tap2_w = t2.dy.data_ptr(), t2.dx.data_ptr(), t2.w.data_ptr()
-        p.ntaps, p.halo = t.n, t.halo
-        p.tap_dy, p.tap_dx, p.tap_w = t.dy.data_ptr(), t.dx.data_ptr(), t.w.data_ptr()
-        fold = operator.folded_bases() if (cov.use_dct and p.op in (1, 5, 8)) else None
-        if fold is not None:  # separable blur absorbed by the DCT passes of A C A^T (measurements.folded_dct_blur_bases)
-            mats, sym = fold
-            p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in mats)
-            p.fold_sym = int(sym)
-            keep.extend(mats)
-        sr = operator.folded_sr_bases() if (cov.use_dct and operator.name in ("custom_sr", "weighted_sr")) else None
-        if sr is not None:  # rank-1 PSF + decimation absorbed by rectangular DCT bases (measurements.folded_dct_sr_bases)
-            p.op = 7 if p.op == 2 else 11
-            p.fold_fwd_w, p.fold_fwd_h, p.fold_inv_w, p.fold_inv_h = (f.data_ptr() for f in sr)
-            keep.extend(sr)
-    if operator.name == "masked_blur":  # A = M B: the mask rides with the blur's fields (ops 5 / 6); kept LAST in `keep`
-        mask = operator.mask.to(device=cov.device, dtype=F64).contiguous()
-        p.mask = mask.data_ptr()
-        keep.append(mask)
-    if operator.name in _WEIGHTED:  # the weights 1 / sigma_i ride in the mask field (ops 8 .. 11); kept LAST in `keep`
-        w = operator.weights.to(device=cov.device, dtype=F64).contiguous()
-        p.mask = w.data_ptr()
-        keep.append(w)
-    return p, keep
+    if row.layout in _FILL:
+        _FILL[row.layout](p, keep, operator, cov, row)
+    rides = None
+    if row.rides is not None:
+        rides = getattr(operator, row.rides).to(device=cov.device, dtype=F64).contiguous()
+        p.mask = rides.data_ptr()
+        keep.append(rides)
+    return _System(p, keep, rides)
+
+
+def _problem(operator, cov, sigma_y2):
+    """(FhProblem, the tensors it points to) of an operator's system on a covariance"""
+    system = _system(operator, cov, sigma_y2)
+    return system.problem, system.keep
 
 
 def _solver_sigma_y2(operator):
-    """sigma_y2 of the system the device solves: `_sigma_y2`, or 1 for the whitened system of a noise-map operator (its
-    `sigma_s` is not read)"""
-    if operator.name in _FOURIER:  # the mask alone: the scalar level under the blur rule; a noise map: the whitened system
-        return 1.0 if operator.noise_map is not None else _sigma_y2(operator)
-    return 1.0 if operator.name in _WEIGHTED else _sigma_y2(operator)
+    """sigma_y2 of the system the device solves: `_sigma_y2`, or 1 for the whitened system of a noise map (the operator's
+    `sigma_s` is then not read)"""
+    unit = _OPS[operator.name].unit_sigma
+    if unit == "always" or (unit == "noise_map" and operator.noise_map is not None):
+        return 1.0
+    return _sigma_y2(operator)
 
 
 def _sigma_y2(operator):
     """`sigma_s.clip(min=0.001)**2` evaluated in float32 like the reference (:386, :491), SR also clips at 1e-2 (:642);
     colorization and denoising follow the blur / inpainting rule."""
     s = operator.sigma_s.detach().cpu().float().clip(min=0.001)
-    if operator.name in _DECIMATING:
+    if getattr(_OPS.get(operator.name), "decimating", False):
         s = s.clip(min=1e-2)
     return float((s ** 2).item())
+
+
+def _stacked(per_image, like):
+    """the B images' masks or weights as one tensor of `like`'s shape (None without any)"""
+    if not per_image:
+        return None
+    return per_image[0].view_as(like) if len(per_image) == 1 else torch.cat([k.view(1, *like.shape[1:]) for k in per_image], 0)
+
+
+def _rhs(ctx, row, operator, per_image, y64, x64, apply_ctx=None):
+    """b = [W] (y - A x0) of the B >= 1 images stacked in y64 and x64, through `ctx`'s fh_axpby"""
+    if row.layout == "mask":
+        mask = _stacked(per_image, x64)
+        return ctx.axpby(1.0, (mask * y64).contiguous(), -1.0, (mask * x64).contiguous(), torch.empty_like(x64))
+    ax = operator.apply(x64, ctx=apply_ctx)
+    b = ctx.axpby(1.0, y64, -1.0, ax, ax)
+    if per_image:  # b = M (y - B x0); noise map: the whitened b = W (y - A0 x0); each image with its own
+        b = (_stacked(per_image, b) * b).contiguous()
+    return b
+
+
+def _mat(row, operator, per_image, sol, apply_ctx=None):
+    """mat = A^T [W] u of the CG solution(s) u"""
+    if row.layout == "mask":
+        return sol
+    if row.rides == "weights":  # mat = A0^T W u
+        sol = (_stacked(per_image, sol) * sol).contiguous()
+    return operator.apply(sol, adjoint=True, ctx=apply_ctx)
 
 
 def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, info_out=None, rtol=None, scipy_cg=False,
@@ -215,25 +283,15 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
     cov = covariance_model
     ctx = cov.ctx
     dev = cov.device
-    name = operator.name
-    if _op_code(name) is None:
+    row = _OPS.get(operator.name)
+    if row is None:
         raise ValueError(_BAD_OPERATOR)
-    prob, keep = _problem(operator, cov, _solver_sigma_y2(operator))
+    prob, _keep, rides = _system(operator, cov, _solver_sigma_y2(operator))
+    per_image = [] if rides is None else [rides]
     prob.cg_scipy = int(bool(scipy_cg))
     y64 = y.detach().to(device=dev, dtype=F64).contiguous()
     x64 = x0_mean.detach().to(device=dev, dtype=F64).contiguous()
-    # b = y - A x0_mean
-    if name in _MASKED:
-        mask = keep[-1].view_as(x64)
-        b = ctx.axpby(1.0, (mask * y64).contiguous(), -1.0, (mask * x64).contiguous(), torch.empty_like(x64))
-    elif name == "colorization":  # one measurement plane per image
-        ax = operator._mix(x64)
-        b = ctx.axpby(1.0, y64, -1.0, ax, ax)
-    else:
-        ax = operator._conv(x64, stride=prob.stride)
-        b = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur" or _whitened(name):  # b = M (y - B x0); noise map: the whitened b = W (y - A0 x0)
-            b = (keep[-1].view_as(b) * b).contiguous()
+    b = _rhs(ctx, row, operator, per_image, y64, x64)
     sol = torch.empty_like(b)
     info = _lib.FhCgInfo()
     rtol = rtol_func(sigma_t, max_rtol) if rtol is None else rtol
@@ -241,19 +299,13 @@ def solve_customcuda(operator, y, x0_mean, covariance_model, max_rtol, sigma_t, 
         maxiter = 1000 if scipy_cg else 5000
     _lib.check(ctx.lib.fh_cg_solve(ctx.h, C.byref(prob), b.data_ptr(), sol.data_ptr(), rtol, 0.0, maxiter,
                                    C.byref(info), _lib.stream()), "fh_cg_solve")
-    if info.niter == (1000 if scipy_cg else (5000 if name in _MASKED else 2000)):  # the reference's (inconsistent) guards
+    if info.niter == (1000 if scipy_cg else (5000 if row.layout == "mask" else 2000)):  # the reference's (inconsistent) guards
         warn("CG not converge.")
     if info_out is not None:
         info_out.append({"niter": info.niter, "optimal": bool(info.optimal), "residual_norm": info.residual_norm,
                          "rtol": rtol})
     solve_customcuda.last_solution = sol  # the measurement-space CG solution u (mat = A^T u); read by the parity tests
-    if name in _MASKED:
-        return sol
-    if name == "colorization":
-        return operator._mix(sol, adjoint=True)
-    if _whitened(name):  # mat = A0^T W u
-        sol = (keep[-1].view_as(sol) * sol).contiguous()
-    return operator._conv(sol, stride=prob.stride, adjoint=True)
+    return _mat(row, operator, per_image, sol)
 
 
 solve_customcuda.last_solution = None
@@ -267,7 +319,8 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     B = len(operators)
     op0, cov0 = operators[0], covariance_models[0]
     name = op0.name
-    if _op_code(name) is None:
+    row = _OPS.get(name)
+    if row is None:
         raise ValueError(_BAD_OPERATOR)
     dev, S = cov0.device, cov0.S
     # scratch sized for the whole batch; one context per lock-step GROUP (keyed by the group's first image slot), so
@@ -276,77 +329,26 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     # `exclusive`: nothing else synchronises across workgroups on this GPU while the solve runs (the lock-step sampler
     # has joined its per-image streams) -> the covariance apply inside CG reads each factor base once, not twice
     ctx.set_exclusive(exclusive)
-    prob, keep = _problem(op0, cov0, _solver_sigma_y2(op0))
-    blend = keep[-1] if name == "varying_blur" else None  # op 14: _problem keeps the device blend maps last
+    prob, keep, _rides = _system(op0, cov0, _solver_sigma_y2(op0))
     per = _lib.FhBatch()
     per.nimg = B
     m = cov0.famC.m
+    per_image = []  # every image brings its own mask or noise map (fourier_sampling: its own sampling mask)
     for b, (op, cov) in enumerate(zip(operators, covariance_models)):
         assert op.name == name and cov.famC.m == m and cov.C.M_dev.shape[1] == cov0.C.M_dev.shape[1], \
             "lock-step images must share operator type and factor count"
         per.D[b], per.r[b], per.B[b], per.M[b] = (cov.C.D.data_ptr(), cov.C.r.data_ptr(), cov.famC.B.data_ptr(),
                                                   cov.C.M_dev.data_ptr())
-        if name == "colorization":
-            assert op.channel_weights == op0.channel_weights, "lock-step images must share the channel weights"
-        if name in _SHARED_PSF:
-            assert torch.equal(op.taps.kernel, op0.taps.kernel), "lock-step images must share the PSF"
-        if name in _BURST:
-            assert op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in
-                                                     zip(op.kernels, op0.kernels)), \
-                "lock-step images must share the PSF of every frame"
-        if name == "varying_blur":
-            assert op.nframes == op0.nframes and all(a.shape == b.shape and np.array_equal(a, b) for a, b in
-                                                     zip(op.kernels, op0.kernels)), \
-                "lock-step images must share every PSF"
-            assert op.blend.shape == op0.blend.shape and torch.equal(op.blend, op0.blend), \
-                "lock-step images must share the blend maps"
-        if name in _DECIMATING:
-            assert op.scale_factor == op0.scale_factor, "lock-step images must share the scale_factor"
-        if name in _MASKED or name == "masked_blur":
-            mk = op.mask.to(device=dev, dtype=F64).contiguous()
+        for what in row.shares:
+            assert _SHARED[what](op, op0, S), f"lock-step images must {what}"
+        if row.rides is not None:
+            mk = getattr(op, row.rides).to(device=dev, dtype=F64).contiguous()
             keep.append(mk)
-            per.mask[b] = mk.data_ptr()
-        if name in _FOURIER:
-            assert op.in_shape[-1] == S and op0.in_shape[-1] == S, "lock-step images must share the image side"
-            assert (op.noise_map is None) == (op0.noise_map is None) and _solver_sigma_y2(op) == prob.sigma_y2, \
-                "lock-step images must all carry a noise map or share the noise level"
-        if _whitened(name):  # every image brings its own noise map (fourier_sampling: its own sampling mask)
-            mk = op.weights.to(device=dev, dtype=F64).contiguous()
-            keep.append(mk)
+            per_image.append(mk)
             per.mask[b] = mk.data_ptr()
     y64 = torch.cat([y.detach().to(device=dev, dtype=F64) for y in ys], 0).contiguous()
     x64 = torch.cat([x.detach().to(device=dev, dtype=F64) for x in x0_means], 0).contiguous()
-    planes = 3 * B
-
-    def conv(v, adjoint):
-        """op0's blur on the whole batch (planes = 3B)"""
-        so = S if (adjoint or prob.stride == 1) else S // prob.stride
-        if name in _BURST:  # all frames of all images: [B,3,S,S] <-> [B,3K,So,So]
-            out = torch.empty(B, 3 if adjoint else 3 * op0.nframes, so, so, dtype=F64, device=dev)
-            return ctx.blur_frames(v, out, op0.frame_taps, planes, prob.stride, adjoint)
-        out = torch.empty(B, 3, so, so, dtype=F64, device=dev)
-        if name in _FOURIER:  # the Hartley transform, its own adjoint
-            return ctx.hartley2d(v, out, op0.folded_hartley_bases(False, dev)[0])
-        if name == "varying_blur":  # the blended PSFs, the maps shared by the images
-            return ctx.blur_blend(v, out, op0.frame_taps, blend, planes, adjoint)
-        return ctx.blur(v, out, op0.taps, planes, prob.stride, adjoint)
-
-    def mix(v, adjoint):
-        """op0's channel mix on the whole batch"""
-        out = torch.empty(B, 3 if adjoint else 1, S, S, dtype=F64, device=dev)
-        return ctx.channel_mix(v, out, op0.weights, adjoint)
-
-    if name in _MASKED:
-        mask = torch.cat([k.view(1, 3, S, S) for k in keep[-B:]], 0)
-        b_vec = ctx.axpby(1.0, (mask * y64).contiguous(), -1.0, (mask * x64).contiguous(), torch.empty_like(x64))
-    elif name == "colorization":
-        ax = mix(x64, False)
-        b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
-    else:
-        ax = conv(x64, False)
-        b_vec = ctx.axpby(1.0, y64, -1.0, ax, ax)
-        if name == "masked_blur" or _whitened(name):  # b = M (y - B x0) / W (y - A0 x0), each image with its own map
-            b_vec = (torch.cat([k.view(1, *b_vec.shape[1:]) for k in keep[-B:]], 0) * b_vec).contiguous()
+    b_vec = _rhs(ctx, row, op0, per_image, y64, x64, apply_ctx=ctx)  # op0's apply on the whole batch (planes = 3 B)
     sol = torch.empty_like(b_vec)
     rtol = rtol_func(sigma_t, max_rtol)
     rtols = (C.c_double * B)(*([rtol] * B))
@@ -354,16 +356,12 @@ def solve_customcuda_batched(operators, ys, x0_means, covariance_models, max_rto
     _lib.check(ctx.lib.fh_cg_solve_batched(ctx.h, C.byref(prob), C.byref(per), b_vec.data_ptr(), sol.data_ptr(), rtols,
                                            0.0, 5000, infos, _lib.stream()), "fh_cg_solve_batched")
     for b in range(B):
-        if infos[b].niter == (5000 if name in _MASKED else 2000):
+        if infos[b].niter == (5000 if row.layout == "mask" else 2000):
             warn("CG not converge.")
         if infos_out is not None:
             infos_out.append({"niter": infos[b].niter, "optimal": bool(infos[b].optimal),
                               "residual_norm": infos[b].residual_norm, "rtol": rtol})
-    if name in _MASKED:
-        return sol
-    if _whitened(name):  # mat = A0^T W u
-        sol = (torch.cat([k.view(1, *sol.shape[1:]) for k in keep[-B:]], 0) * sol).contiguous()
-    return mix(sol, True) if name == "colorization" else conv(sol, True)
+    return _mat(row, op0, per_image, sol, apply_ctx=ctx)
 
 
 def choose_solver(operator_name, operator, y, x0_mean, theta0_var=None, covariance_model=None, method="customcuda",

@@ -9,8 +9,9 @@ so the operators carry a sparse tap list (`taps`) that libfh_hip.so consumes.  `
 """
 from __future__ import annotations
 
+import ctypes
+import hashlib
 import os
-from functools import partial
 
 import numpy as np
 import scipy.io
@@ -41,19 +42,97 @@ def get_operator(name, **kwargs):
     return __OPERATOR__[name](**kwargs)
 
 
+# ---------------------------------------------------------------------------------------------- argument checks
+# Written once for the operators below; each takes the operator's name (`who`) for its messages.
+def _checked_psf(k, who, what="the PSF", shifted=False, max_taps=None):
+    """`k` rounded to float32 like the shipped PSFs, after the checks every caller's PSF passes: finite (also once rounded), not all
+    zero, at most 32 from its centre at index size // 2 and, for a tap-list-only operator, at most `max_taps` non-zeros"""
+    with np.errstate(over="ignore"):
+        k = np.asarray(k, dtype=np.float32)
+    if not np.isfinite(k).all():
+        raise ValueError(f"{who}: {what} has a non-finite entry (also after rounding to float32)")
+    if not k.any():
+        raise ValueError(f"{who}: {what} is all zero")
+    ys, xs = np.nonzero(k)
+    hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
+    if max(hy, hx) > 32:
+        raise ValueError(f"{who}: {what} reaches ({hy}, {hx}) samples from its centre at index size // 2" +
+                         (" (its shift included); the kernels stage at most 32" if shifted else
+                          "; the kernels stage at most 32 (PSFs up to 65 x 65)"))
+    if max_taps is not None and ys.size > max_taps:
+        raise ValueError(f"{who}: {what} has {ys.size} non-zeros, a tap list holds {max_taps}")
+    return k
+
+
+def _load_psfs(who, kernels, kernel_path, each):
+    """K PSFs as float64 arrays from `kernels` (K 2-D arrays, a [K, kh, kw] array or one 2-D array) or from a .npy of the same;
+    the caller has checked that exactly one of the two is given"""
+    if kernels is None:
+        arr = np.load(kernel_path)
+        if arr.ndim not in (2, 3):
+            raise ValueError(f"{who}: {kernel_path} must hold a [K, kh, kw] array or one 2-D PSF, got shape {tuple(arr.shape)}")
+        psfs = [arr] if arr.ndim == 2 else list(arr)
+    else:
+        psfs = [kernels] if (isinstance(kernels, np.ndarray) and kernels.ndim == 2) else list(kernels)
+    psfs = [np.asarray(k, dtype=np.float64) for k in psfs]
+    if not psfs or any(k.ndim != 2 or k.size == 0 for k in psfs):
+        raise ValueError(f"{who}: every {each} must be a non-empty 2-D array")
+    return psfs
+
+
+def _integer(s):
+    """int(s) of an integral number that is no bool, else None"""
+    ok = isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, bool) and float(s) == int(s)
+    return int(s) if ok else None
+
+
+def _check_factor(who, S, s):
+    """the scale factor s divides the image side S and leaves at least 8 x 8 measurements"""
+    if S % s != 0:
+        raise ValueError(f"{who}: scale_factor {s} does not divide the image side {S}")
+    if S // s < 8:
+        raise ValueError(f"{who}: scale_factor {s} leaves a {S // s} x {S // s} measurement of a {S} x {S} image; at "
+                         "least 8 x 8 is required")
+
+
+def _plan_refusal(plan, *args):
+    """(adjoint, code) of the first direction for which the library's launch plan `plan(*args, adjoint, out)` finds no kernel,
+    None when both run; asked of the library itself, which needs no device"""
+    fn, out = getattr(_lib.load(), plan), (ctypes.c_int32 * 6)()
+    for adjoint in (0, 1):
+        rc = fn(*args, adjoint, out)
+        if rc != 0:
+            return adjoint, rc
+    return None
+
+
+def _load_array(who, what, value, path, shapes=None):
+    """an array, a tensor or the .npy at `path` (when `value` is None), with one of `shapes` if given; float64"""
+    a = np.load(path) if value is None else (value.detach().cpu().numpy() if torch.is_tensor(value) else np.asarray(value))
+    if shapes is not None and tuple(a.shape) not in shapes:
+        raise ValueError(f"{who}: {what} must have shape " + ", ".join(str(s) for s in shapes[:-1]) +
+                         f" or {shapes[-1]}, got {tuple(a.shape)}")
+    return np.asarray(a, dtype=np.float64)
+
+
+def _image_shapes(n):
+    return (n, n), (3, n, n), (1, 3, n, n)
+
+
 class _TapList:
     def __init__(self, k, device):
         ys, xs = np.nonzero(k)
         cy, cx = k.shape[0] // 2, k.shape[1] // 2
+        dy, dx, w = (ys - cy).astype(np.int32), (xs - cx).astype(np.int32), np.ascontiguousarray(k[ys, xs], dtype=np.float64)
+        # what the fold cache knows the list by: equal lists share their folded bases without reading the device copies back
+        self.digest = hashlib.sha1(dy.tobytes() + dx.tobytes() + w.tobytes()).hexdigest()
         self.n = int(ys.size)
         hy, hx = int(np.abs(ys - cy).max()), int(np.abs(xs - cx).max())
         self.hy, self.hx = hy, hx
         # fh_conv_circ halo code: for 1-D lists -(h+1) (column kernel, dx = 0) / -(h+101) (row kernel), else both extents
         # (1000 + 64 hy + hx), so that the kernel stages only the halo the taps reach
         self.halo = -(hy + 1) if (hx == 0 and hy > 0) else (-(hx + 101) if (hy == 0 and hx > 0) else 1000 + 64 * hy + hx)
-        self.dy = torch.from_numpy((ys - cy).astype(np.int32)).to(device)
-        self.dx = torch.from_numpy((xs - cx).astype(np.int32)).to(device)
-        self.w = torch.from_numpy(np.ascontiguousarray(k[ys, xs], dtype=np.float64)).to(device)
+        self.dy, self.dx, self.w = (torch.from_numpy(a).to(device) for a in (dy, dx, w))
 
 
 class Taps(_TapList):
@@ -95,10 +174,7 @@ class Taps(_TapList):
     def _tap_list_fits(self):
         """False where fh_conv_circ has no stride-1 launch for this list (wide extents with several hundred taps overflow the
         tile kernels' LDS: FH_ESIZE); asked of the library's own plan, which needs no device."""
-        import ctypes
-        plan = _lib.load().fh_conv_circ_plan
-        out = (ctypes.c_int32 * 6)()
-        return all(plan(256, self.n, self.halo, 3, 1, adjoint, out) == 0 for adjoint in (0, 1))
+        return _plan_refusal("fh_conv_circ_plan", 256, self.n, self.halo, 3, 1) is None
 
 
 def dct_basis_longdouble(S):
@@ -164,46 +240,85 @@ def pack_symmetric_halves(P):
     return fwd, inv
 
 
-_FOLD_CACHE = {}
+_FOLD_CACHE = {}  # (kind, S, factor, device, digests of the column and row tap lists) -> folded bases on the device
 
 
 class LinearOperator:
+    """What the operators share.  A subclass supplies `apply`; `forward`, `transpose` and `forward_adjoint` follow from it,
+    from `_noise`, from `mask` (where the operator has one it multiplies the adjoint's argument) and from `out_shape` (the
+    measurement's shape, the image's where absent)."""
     device = None
 
     ctx_slot = 0  # scratch-context slot; the batched sampler gives every concurrent image its own
+    decimates = False  # A ends with [..., ::scale_factor, ::scale_factor]
+    keeps_last_y = True  # `forward` remembers its result for `pre_calculated`
 
     def _ctx(self):
         S = self.in_shape[-1]
         return _lib.Context.get(S, 3, 128, self.ctx_slot)
 
-    def _conv(self, x, stride=1, adjoint=False):
-        """float64 circular convolution of an NCHW tensor (N = 1) with self.taps; returns float64."""
+    def apply(self, x, adjoint=False, ctx=None):
+        """A x, or A^T x, of an NCHW tensor with any N, in float64: the noiseless measurement the solver's system is built on.
+        `ctx`: the scratch context to run on, None = the operator's own choice (the batched solve passes its batch's)."""
+        return self._conv(x, self.scale_factor if self.decimates else 1, adjoint, ctx)
+
+    def _conv(self, x, stride=1, adjoint=False, ctx=None):
+        """float64 circular convolution of an NCHW tensor with self.taps; returns float64."""
         S = self.in_shape[-1]
         x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
         so = S if (adjoint or stride == 1) else S // stride
         out = torch.empty(x64.shape[0], x64.shape[1], so, so, dtype=F64, device=self.device)
         planes = x64.shape[0] * x64.shape[1]
-        return self._ctx().blur(x64, out, self.taps, planes, stride, adjoint)
+        return (self._ctx() if ctx is None else ctx).blur(x64, out, self.taps, planes, stride, adjoint)
+
+    def forward(self, data, flatten=False, noiseless=False):
+        # the noise is drawn once, at the measurement's shape (an operator's mask or noise map comes in through `_noise`)
+        y = self._noise(self.apply(data).to(data.dtype), noiseless)
+        if self.keeps_last_y:
+            self._last_y = y
+        if flatten:
+            return y, y.reshape(y.shape[0], -1)
+        return y
+
+    def _apply_adjoint(self, v):
+        mask = getattr(self, "mask", None)
+        return self.apply(v if mask is None else v * mask.to(v.dtype), adjoint=True).to(v.dtype)
+
+    def transpose(self, y, flatten=False):
+        if flatten:
+            y = y.reshape(y.shape[0], *getattr(self, "out_shape", self.in_shape)[-3:])
+        return self._apply_adjoint(y)
+
+    def forward_adjoint(self, v):
+        """exact adjoint of the noiseless `forward` (A^T (mask * v) with a mask), for DPS"""
+        return self._apply_adjoint(v)
+
+    def _folded(self, kind, factor, build):
+        """`build(col_dy, col_w, row_dx, row_w)` of the separable PSF's two tap lists, once per (kind, size, factor, device,
+        PSF) and shared by all instances - None when the PSF is not rank-1 or FH_NO_FOLD=1"""
+        sep = getattr(getattr(self, "taps", None), "sep", None)
+        if sep is None or os.environ.get("FH_NO_FOLD") == "1":
+            return None
+        col, row = sep
+        key = (kind, self.in_shape[-1], factor, str(self.device), col.digest, row.digest)
+        if key not in _FOLD_CACHE:
+            _FOLD_CACHE[key] = build(col.dy.cpu().numpy(), col.w.cpu().numpy(), row.dx.cpu().numpy(), row.w.cpu().numpy())
+        return _FOLD_CACHE[key]
 
     def folded_bases(self):
         """(device copies of `folded_dct_blur_bases` for this operator's separable PSF, packed-symmetric flag) - None when
         the PSF is not rank-1 or the operator decimates; built once per (PSF, size, device), shared by all instances."""
-        sep = getattr(getattr(self, "taps", None), "sep", None)
-        if sep is None or self.name == "super_resolution" or os.environ.get("FH_NO_FOLD") == "1":
-            return None
-        S = self.in_shape[-1]
-        col, row = sep
-        key = (S, str(self.device), col.dy.cpu().numpy().tobytes(), col.w.cpu().numpy().tobytes(),
-               row.dx.cpu().numpy().tobytes(), row.w.cpu().numpy().tobytes())
-        if key not in _FOLD_CACHE:
-            mats = folded_dct_blur_bases(col.dy.cpu().numpy(), col.w.cpu().numpy(), row.dx.cpu().numpy(),
-                                         row.w.cpu().numpy(), S)
+        def build(*lists):
+            mats = folded_dct_blur_bases(*lists, self.in_shape[-1])
             hw, hh = pack_symmetric_halves(mats[0]), pack_symmetric_halves(mats[1])
             sym = hw is not None and hh is not None and os.environ.get("FH_DCT_NOSYM") is None
             if sym:  # (fold_fwd_w, fold_fwd_h, fold_inv_w, fold_inv_h) as packed halves
                 mats = (hw[0], hh[0], hw[1], hh[1])
-            _FOLD_CACHE[key] = (tuple(torch.from_numpy(m).to(self.device) for m in mats), sym)
-        return _FOLD_CACHE[key]
+            return tuple(torch.from_numpy(m).to(self.device) for m in mats), sym
+        return None if self.decimates else self._folded("blur", 1, build)
+
+    def folded_sr_bases(self):
+        return None  # (only a single rank-1 PSF with a decimation folds into rectangular bases: CustomSROperator)
 
     def _noise(self, y, noiseless):
         if not noiseless:
@@ -223,7 +338,7 @@ class LinearOperator:
         y = getattr(self, "_last_y", None)
         FBFy = None
         if y is not None:
-            sf = getattr(self, "scale_factor", 1) if self.name in ("super_resolution", "custom_sr", "weighted_sr") else 1
+            sf = self.scale_factor if self.decimates else 1
             up = torch.zeros(y.shape[0], y.shape[1], S, S, device=self.device, dtype=y.dtype)
             up[..., ::sf, ::sf] = y
             FBFy = FBC * torch.fft.fftn(up, dim=(-2, -1))
@@ -240,22 +355,6 @@ class _BlurOperator(LinearOperator):
         self.taps = Taps(self.kernel, self.device)
         self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
         self.in_shape = in_shape
-
-    def forward(self, data, flatten=False, noiseless=False):
-        y = self._noise(self._conv(data).to(data.dtype), noiseless)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.in_shape[-3:])
-        return self._conv(y, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`, for DPS"""
-        return self._conv(v, adjoint=True).to(v.dtype)
 
     def get_kernel(self):
         return self.taps.kernel.view(1, 1, *self.taps.kernel.shape).to(self.device)
@@ -284,16 +383,7 @@ class CustomBlurOperator(_BlurOperator):
         k = np.load(kernel_path) if kernel is None else np.asarray(kernel)
         if k.ndim != 2 or k.size == 0:
             raise ValueError(f"custom_blur: the PSF must be a 2-D array, got shape {tuple(k.shape)}")
-        k = np.asarray(k, dtype=np.float32)
-        if not np.isfinite(k).all():
-            raise ValueError("custom_blur: the PSF has a non-finite entry (also after rounding to float32)")
-        if not k.any():
-            raise ValueError("custom_blur: the PSF is all zero")
-        ys, xs = np.nonzero(k)
-        hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
-        if max(hy, hx) > 32:
-            raise ValueError(f"custom_blur: the PSF reaches ({hy}, {hx}) samples from its centre at index size // 2; the "
-                             "kernels stage at most 32 (PSFs up to 65 x 65)")
+        k = _checked_psf(k, "custom_blur")
         self.device = torch.device(device)
         self.kernel_size = tuple(k.shape)  # (rows, columns)
         self.kernel = k
@@ -328,11 +418,7 @@ class MaskedBlurOperator(CustomBlurOperator):
             raise ValueError(f"masked_blur: mask_border is a pixel count >= 0, or -1 for the PSF's reach; got {mask_border}")
         m = np.ones((1, 3, S, S))
         if mask is not None or mask_path is not None:
-            a = np.load(mask_path) if mask is None else (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask))
-            if tuple(a.shape) not in ((S, S), (3, S, S), (1, 3, S, S)):
-                raise ValueError(f"masked_blur: the mask must have shape ({S}, {S}), (3, {S}, {S}) or (1, 3, {S}, {S}), got "
-                                 f"{tuple(a.shape)}")
-            a = np.asarray(a, dtype=np.float64)
+            a = _load_array("masked_blur", "the mask", mask, mask_path, _image_shapes(S))
             if not np.isfinite(a).all():
                 raise ValueError("masked_blur: the mask has a non-finite entry")
             if not np.isin(a, (0.0, 1.0)).all():
@@ -352,25 +438,9 @@ class MaskedBlurOperator(CustomBlurOperator):
         self.mask_border = (by, bx)
         self.mask = torch.from_numpy(m).to(self.device)  # float64 [1,3,S,S]
 
-    def forward(self, data, flatten=False, noiseless=False):
+    def _noise(self, y, noiseless):
         # the noise is drawn for the full image (custom_blur's RNG consumption), then masked
-        y = self._noise(self._conv(data).to(data.dtype), noiseless) * self.mask.to(data.dtype)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.in_shape[-3:])
-        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`: B^T (mask * v)"""
-        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
-
-
-_SR_FOLD_CACHE = {}
+        return super()._noise(y, noiseless) * self.mask.to(y.dtype)
 
 
 @register_operator(name="custom_sr")
@@ -382,70 +452,33 @@ class CustomSROperator(CustomBlurOperator):
     Every route outside the folded solve runs the PSF's tap list (k_conv_dec / k_conv_up), so the PSF has at most
     `Taps.MAX_TAPS` non-zeros; a rank-1 PSF (box, Gaussian, binomial) additionally folds into rectangular DCT bases
     (`folded_sr_bases`, fh_problem.op = 7)."""
+    decimates = True
 
     def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernel_path=None, kernel=None, **kwargs):
-        s = scale_factor
-        ok = isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, bool) and float(s) == int(s)
-        if ok and int(s) == 1:
+        s = _integer(scale_factor)
+        if s == 1:
             raise ValueError("custom_sr: scale_factor = 1 does not decimate - use custom_blur for a blur at full resolution")
-        if not ok or not 2 <= int(s) <= 16:
+        if s is None or not 2 <= s <= 16:
             raise ValueError(f"custom_sr: scale_factor must be an integer from 2 to 16, got {scale_factor!r}")
-        s = int(s)
         super().__init__(in_shape, sigma_s, device, kernel_path=kernel_path, kernel=kernel)
         S = int(in_shape[-1])
-        if S % s != 0:
-            raise ValueError(f"custom_sr: scale_factor {s} does not divide the image side {S}")
-        if S // s < 8:
-            raise ValueError(f"custom_sr: scale_factor {s} leaves a {S // s} x {S // s} measurement of a {S} x {S} image; at "
-                             "least 8 x 8 is required")
+        _check_factor("custom_sr", S, s)
         if self.taps.n > Taps.MAX_TAPS:
             raise ValueError(f"custom_sr: the PSF has {self.taps.n} non-zeros, a tap list holds {Taps.MAX_TAPS}; a decimating "
                              "dense-window kernel is out of scope")
-        import ctypes
-        plan, out = _lib.load().fh_conv_circ_plan, (ctypes.c_int32 * 6)()
-        for adjoint in (0, 1):
-            rc = plan(S, self.taps.n, self.taps.halo, 3, s, adjoint, out)
-            if rc != 0:
-                raise ValueError(f"custom_sr: no kernel runs this PSF's tap list ({self.taps.n} taps reaching ({self.taps.hy}, "
-                                 f"{self.taps.hx})) at stride {s} on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
+        refused = _plan_refusal("fh_conv_circ_plan", S, self.taps.n, self.taps.halo, 3, s)
+        if refused:
+            raise ValueError(f"custom_sr: no kernel runs this PSF's tap list ({self.taps.n} taps reaching ({self.taps.hy}, "
+                             f"{self.taps.hx})) at stride {s} on a {S} x {S} image (adjoint = {refused[0]}, code {refused[1]})")
         self.scale_factor = s
         self.out_shape = (1, 3, S // s, S // s)
-
-    def forward(self, data, flatten=False, noiseless=False):
-        # the noise is drawn at the low-resolution shape
-        y = self._noise(self._conv(data, stride=self.scale_factor).to(data.dtype), noiseless)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.out_shape[-3:])
-        return self._conv(y, stride=self.scale_factor, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`, for DPS"""
-        return self._conv(v, stride=self.scale_factor, adjoint=True).to(v.dtype)
-
-    def folded_bases(self):
-        return None  # (the stride-1 fold does not apply to a decimating operator)
 
     def folded_sr_bases(self):
         """device copies of `folded_dct_sr_bases` (G_row, G_col, G_row^T, G_col^T) for a rank-1 PSF - None when the PSF is not
         rank-1 or FH_NO_FOLD=1; built once per (PSF, size, factor, device), shared by all instances."""
-        sep = self.taps.sep
-        if sep is None or os.environ.get("FH_NO_FOLD") == "1":
-            return None
         S, s = self.in_shape[-1], self.scale_factor
-        col, row = sep
-        key = (S, s, str(self.device), col.dy.cpu().numpy().tobytes(), col.w.cpu().numpy().tobytes(),
-               row.dx.cpu().numpy().tobytes(), row.w.cpu().numpy().tobytes())
-        if key not in _SR_FOLD_CACHE:
-            mats = folded_dct_sr_bases(col.dy.cpu().numpy(), col.w.cpu().numpy(), row.dx.cpu().numpy(), row.w.cpu().numpy(),
-                                       S, s)
-            _SR_FOLD_CACHE[key] = tuple(torch.from_numpy(m).to(self.device) for m in mats)
-        return _SR_FOLD_CACHE[key]
+        return self._folded("sr", s, lambda *lists: tuple(torch.from_numpy(m).to(self.device)
+                                                          for m in folded_dct_sr_bases(*lists, S, s)))
 
 
 def shifted_psf(psf, dy, dx):
@@ -516,8 +549,34 @@ def parse_frame_shifts(shifts):
     return out
 
 
+class _ImageOperator(LinearOperator):
+    """Operators whose kernels take whole images [N, 3, S, S] and check the planes their context holds (fh_conv_frames,
+    fh_conv_blend, fh_hartley2d)."""
+
+    def _conv(self, x, stride=None, adjoint=False, ctx=None):
+        """`apply` under the name the tap-list operators use (`stride` is the operator's own whatever the caller passes)"""
+        return self.apply(x, adjoint, ctx)
+
+    def _images(self, x, shape, ctx):
+        """(x in float64 on the device, N, the context for its 3 N planes) after the shape check [N, *shape]"""
+        S = self.in_shape[-1]
+        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
+        N = x64.shape[0]
+        assert tuple(x64.shape[1:]) == shape, f"{self.name}: expected [N,{','.join(str(n) for n in shape)}], got {tuple(x64.shape)}"
+        if ctx is None:
+            ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)
+        return x64, N, ctx
+
+    def _set_frames(self, psfs, who, what, shifted=False):
+        """`kernels`, `frames` (`Taps` each) and `frame_taps` of K PSFs, each through `_checked_psf` as `what.format(index)`"""
+        self.kernels = [_checked_psf(k, who, what.format(i), shifted, Taps.MAX_TAPS) for i, k in enumerate(psfs)]
+        self.frames = [Taps(k, self.device) for k in self.kernels]
+        self.frame_taps = FrameTaps(self.frames, self.device)
+        self.nframes = len(psfs)
+
+
 @register_operator(name="burst_sr")
-class BurstSROperator(LinearOperator):
+class BurstSROperator(_ImageOperator):
     """Multi-frame super-resolution: K low-resolution frames of one scene, each with its own PSF,
         y_k = (B_k x)[..., ::s, ::s] + sigma_s n_k,   k = 0 .. K - 1,
     B_k the circular blur of `custom_blur` (centre at index size // 2, rounded to float32, used as given), s = `scale_factor`
@@ -530,32 +589,18 @@ class BurstSROperator(LinearOperator):
     One sigma_s covers all frames.  The measurement is frame-major: [1, 3 K, So, So] with channel 3 k + c.  `forward` and
     `transpose` are one A (fh_conv_frames); the solver's system is fh_problem.op = 12.  Every frame's PSF has at most
     `Taps.MAX_TAPS` non-zeros and reaches at most 32 from its centre."""
+    decimates = True
 
     def __init__(self, in_shape, sigma_s, device, scale_factor=None, kernels=None, kernel_path=None, frame_shifts=None, **kwargs):
-        s = scale_factor
-        ok = isinstance(s, (int, float, np.integer, np.floating)) and not isinstance(s, bool) and float(s) == int(s)
-        if not ok or int(s) not in (2, 3, 4):
+        s = _integer(scale_factor)
+        if s not in (2, 3, 4):
             raise ValueError(f"burst_sr: scale_factor must be 2, 3 or 4, got {scale_factor!r}")
-        s = int(s)
         S = int(in_shape[-1])
-        if S % s != 0:
-            raise ValueError(f"burst_sr: scale_factor {s} does not divide the image side {S}")
-        if S // s < 8:
-            raise ValueError(f"burst_sr: scale_factor {s} leaves a {S // s} x {S // s} measurement of a {S} x {S} image; at "
-                             "least 8 x 8 is required")
+        _check_factor("burst_sr", S, s)
         if (kernel_path is None or kernel_path == "") == (kernels is None):
             raise ValueError("burst_sr needs exactly one of kernels (K 2-D arrays) and kernel_path (a .npy file with a "
                              "[K, kh, kw] array, or one 2-D PSF beside frame_shifts)")
-        if kernels is None:
-            arr = np.load(kernel_path)
-            if arr.ndim not in (2, 3):
-                raise ValueError(f"burst_sr: {kernel_path} must hold a [K, kh, kw] array or one 2-D PSF, got shape {tuple(arr.shape)}")
-            psfs = [arr] if arr.ndim == 2 else list(arr)
-        else:
-            psfs = [kernels] if (isinstance(kernels, np.ndarray) and kernels.ndim == 2) else list(kernels)
-        psfs = [np.asarray(k, dtype=np.float64) for k in psfs]
-        if not psfs or any(k.ndim != 2 or k.size == 0 for k in psfs):
-            raise ValueError("burst_sr: every frame's PSF must be a non-empty 2-D array")
+        psfs = _load_psfs("burst_sr", kernels, kernel_path, "frame's PSF")
         if frame_shifts is not None and not (isinstance(frame_shifts, str) and frame_shifts == ""):
             shifts = parse_frame_shifts(frame_shifts)
             if len(psfs) == 1:
@@ -569,75 +614,25 @@ class BurstSROperator(LinearOperator):
             raise ValueError(f"burst_sr: {K} frames at scale_factor {s}; the number of frames K is 1 .. s^2 = {s * s} (the "
                              "measurement is never longer than the image)")
         self.device = torch.device(device)
-        self.frames, self.kernels = [], []
-        for i, k in enumerate(psfs):
-            with np.errstate(over="ignore"):
-                k = np.asarray(k, dtype=np.float32)
-            if not np.isfinite(k).all():
-                raise ValueError(f"burst_sr: the PSF of frame {i} has a non-finite entry (also after rounding to float32)")
-            if not k.any():
-                raise ValueError(f"burst_sr: the PSF of frame {i} is all zero")
-            ys, xs = np.nonzero(k)
-            hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
-            if max(hy, hx) > 32:
-                raise ValueError(f"burst_sr: the PSF of frame {i} reaches ({hy}, {hx}) samples from its centre at index size // 2 "
-                                 "(its shift included); the kernels stage at most 32")
-            if ys.size > Taps.MAX_TAPS:
-                raise ValueError(f"burst_sr: the PSF of frame {i} has {ys.size} non-zeros, a tap list holds {Taps.MAX_TAPS}")
-            self.kernels.append(k)
-            self.frames.append(Taps(k, self.device))
-        self.frame_taps = FrameTaps(self.frames, self.device)
-        import ctypes
-        plan, out = _lib.load().fh_conv_frames_plan, (ctypes.c_int32 * 6)()
+        self._set_frames(psfs, "burst_sr", "the PSF of frame {}", shifted=True)
         ft = self.frame_taps
-        for adjoint in (0, 1):
-            rc = plan(S, K, ft.max_taps, ft.halo, 3, s, adjoint, out)
-            if rc != 0:
-                raise ValueError(f"burst_sr: no kernel runs these tap lists (at most {ft.max_taps} taps per frame reaching "
-                                 f"({ft.hy}, {ft.hx})) at stride {s} on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
-        self.nframes = K
+        refused = _plan_refusal("fh_conv_frames_plan", S, K, ft.max_taps, ft.halo, 3, s)
+        if refused:
+            raise ValueError(f"burst_sr: no kernel runs these tap lists (at most {ft.max_taps} taps per frame reaching "
+                             f"({ft.hy}, {ft.hx})) at stride {s} on a {S} x {S} image (adjoint = {refused[0]}, code {refused[1]})")
         self.scale_factor = s
         self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
         self.in_shape = in_shape
         self.out_shape = (1, 3 * K, S // s, S // s)
 
-    def _conv(self, x, stride=None, adjoint=False):
+    def apply(self, x, adjoint=False, ctx=None):
         """all frames' blur + decimation of an NCHW tensor [N,3,S,S] -> [N,3K,So,So] (frame-major), or the adjoint back;
-        float64.  (`stride` is the operator's own factor whatever the caller passes.)"""
-        S, s, K = self.in_shape[-1], self.scale_factor, self.nframes
-        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
-        N = x64.shape[0]
-        if adjoint:
-            assert tuple(x64.shape[1:]) == (3 * K, S // s, S // s), f"burst_sr: expected [N,{3 * K},{S // s},{S // s}], got {tuple(x64.shape)}"
-            out = torch.empty(N, 3, S, S, dtype=F64, device=self.device)
-        else:
-            assert tuple(x64.shape[1:]) == (3, S, S), f"burst_sr: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
-            out = torch.empty(N, 3 * K, S // s, S // s, dtype=F64, device=self.device)
-        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)  # (fh_conv_frames checks the planes it holds)
+        float64"""
+        S, s = self.in_shape[-1], self.scale_factor
+        y_shape = (3 * self.nframes, S // s, S // s)
+        x64, N, ctx = self._images(x, y_shape if adjoint else (3, S, S), ctx)
+        out = torch.empty(N, *((3, S, S) if adjoint else y_shape), dtype=F64, device=self.device)
         return ctx.blur_frames(x64, out, self.frame_taps, 3 * N, s, adjoint)
-
-    def forward(self, data, flatten=False, noiseless=False):
-        # ONE noise draw at the shape of the whole burst
-        y = self._noise(self._conv(data).to(data.dtype), noiseless)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.out_shape[-3:])
-        return self._conv(y, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`, for DPS"""
-        return self._conv(v, adjoint=True).to(v.dtype)
-
-    def folded_bases(self):
-        return None
-
-    def folded_sr_bases(self):
-        return None  # (a rank-1 fold of the frames into rectangular bases is not built)
 
 
 def grid_blend_weights(S, rows, cols):
@@ -684,7 +679,7 @@ def parse_psf_grid(grid):
 
 
 @register_operator(name="varying_blur")
-class VaryingBlurOperator(LinearOperator):
+class VaryingBlurOperator(_ImageOperator):
     """Blur with a PSF that changes across the field, as the Nagy-O'Leary interpolation of K shift-invariant blurs:
         y = sum_k U_k .* (B_k x) + sigma_s n,   A = sum_k diag(U_k) B_k,   A^T = sum_k B_k^T diag(U_k),
     B_k the circular blur of `custom_blur` with PSF k (centre at index size // 2, rounded to float32, used as given) and U_k a
@@ -707,16 +702,7 @@ class VaryingBlurOperator(LinearOperator):
         if (kernel_path is None or kernel_path == "") == (kernels is None):
             raise ValueError("varying_blur needs exactly one of kernels (K 2-D arrays) and kernel_path (a .npy file with a "
                              "[K, kh, kw] array)")
-        if kernels is None:
-            arr = np.load(kernel_path)
-            if arr.ndim not in (2, 3):
-                raise ValueError(f"varying_blur: {kernel_path} must hold a [K, kh, kw] array or one 2-D PSF, got shape {tuple(arr.shape)}")
-            psfs = [arr] if arr.ndim == 2 else list(arr)
-        else:
-            psfs = [kernels] if (isinstance(kernels, np.ndarray) and kernels.ndim == 2) else list(kernels)
-        psfs = [np.asarray(k, dtype=np.float64) for k in psfs]
-        if not psfs or any(k.ndim != 2 or k.size == 0 for k in psfs):
-            raise ValueError("varying_blur: every PSF must be a non-empty 2-D array")
+        psfs = _load_psfs("varying_blur", kernels, kernel_path, "PSF")
         K = len(psfs)
         if not 1 <= K <= self.MAX_PSFS:
             raise ValueError(f"varying_blur: {K} PSFs; the number of PSFs K is 1 .. {self.MAX_PSFS}")
@@ -729,11 +715,8 @@ class VaryingBlurOperator(LinearOperator):
             if rows * cols != K:
                 raise ValueError(f"varying_blur: psf_grid {rows} x {cols} holds {rows * cols} nodes for {K} PSFs; rows * cols must be K")
             maps = grid_blend_weights(S, rows, cols)
-        elif given[1]:
-            maps = np.load(blend_path)
         else:
-            maps = blend.detach().cpu().numpy() if isinstance(blend, torch.Tensor) else np.asarray(blend)
-        maps = np.asarray(maps, dtype=np.float64)
+            maps = _load_array("varying_blur", "the blend maps", blend, blend_path)
         if tuple(maps.shape) == (K, S, S):
             maps = np.broadcast_to(maps[:, None], (K, 3, S, S))
         elif tuple(maps.shape) in ((K, 3, S, S), (3 * K, S, S)):
@@ -747,70 +730,22 @@ class VaryingBlurOperator(LinearOperator):
             if not maps[i].any():
                 raise ValueError(f"varying_blur: the blend map of PSF {i} is all zero (drop the PSF instead)")
         self.device = torch.device(device)
-        self.frames, self.kernels = [], []
-        for i, k in enumerate(psfs):
-            with np.errstate(over="ignore"):
-                k = np.asarray(k, dtype=np.float32)
-            if not np.isfinite(k).all():
-                raise ValueError(f"varying_blur: PSF {i} has a non-finite entry (also after rounding to float32)")
-            if not k.any():
-                raise ValueError(f"varying_blur: PSF {i} is all zero")
-            ys, xs = np.nonzero(k)
-            hy, hx = int(np.abs(ys - k.shape[0] // 2).max()), int(np.abs(xs - k.shape[1] // 2).max())
-            if max(hy, hx) > 32:
-                raise ValueError(f"varying_blur: PSF {i} reaches ({hy}, {hx}) samples from its centre at index size // 2; the "
-                                 "kernels stage at most 32 (PSFs up to 65 x 65)")
-            if ys.size > Taps.MAX_TAPS:
-                raise ValueError(f"varying_blur: PSF {i} has {ys.size} non-zeros, a tap list holds {Taps.MAX_TAPS}")
-            self.kernels.append(k)
-            self.frames.append(Taps(k, self.device))
-        self.frame_taps = FrameTaps(self.frames, self.device)
-        import ctypes
-        plan, out = _lib.load().fh_conv_blend_plan, (ctypes.c_int32 * 6)()
+        self._set_frames(psfs, "varying_blur", "PSF {}")
         ft = self.frame_taps
-        for adjoint in (0, 1):
-            rc = plan(S, K, ft.max_taps, ft.halo, 3, adjoint, out)
-            if rc != 0:
-                raise ValueError(f"varying_blur: no kernel runs these tap lists (at most {ft.max_taps} taps per PSF reaching "
-                                 f"({ft.hy}, {ft.hx})) on a {S} x {S} image (adjoint = {adjoint}, code {rc})")
-        self.nframes = K
+        refused = _plan_refusal("fh_conv_blend_plan", S, K, ft.max_taps, ft.halo, 3)
+        if refused:
+            raise ValueError(f"varying_blur: no kernel runs these tap lists (at most {ft.max_taps} taps per PSF reaching "
+                             f"({ft.hy}, {ft.hx})) on a {S} x {S} image (adjoint = {refused[0]}, code {refused[1]})")
         self.blend = torch.from_numpy(np.ascontiguousarray(maps)).to(self.device)  # float64 [K, 3, S, S]
         self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
         self.in_shape = in_shape
         self.out_shape = in_shape
 
-    def _conv(self, x, stride=None, adjoint=False):
-        """A (or A^T) of an NCHW tensor [N,3,S,S] -> [N,3,S,S]; float64.  (`stride` is ignored: nothing decimates.)"""
+    def apply(self, x, adjoint=False, ctx=None):
+        """A (or A^T) of an NCHW tensor [N,3,S,S] -> [N,3,S,S]; float64"""
         S = self.in_shape[-1]
-        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
-        N = x64.shape[0]
-        assert tuple(x64.shape[1:]) == (3, S, S), f"varying_blur: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
-        out = torch.empty(N, 3, S, S, dtype=F64, device=self.device)
-        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)  # (fh_conv_blend checks the planes it holds)
-        return ctx.blur_blend(x64, out, self.frame_taps, self.blend, 3 * N, adjoint)
-
-    def forward(self, data, flatten=False, noiseless=False):
-        # ONE noise draw at the image's shape
-        y = self._noise(self._conv(data).to(data.dtype), noiseless)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.in_shape[-3:])
-        return self._conv(y, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`, for DPS"""
-        return self._conv(v, adjoint=True).to(v.dtype)
-
-    def folded_bases(self):
-        return None
-
-    def folded_sr_bases(self):
-        return None
+        x64, N, ctx = self._images(x, (3, S, S), ctx)
+        return ctx.blur_blend(x64, torch.empty_like(x64), self.frame_taps, self.blend, 3 * N, adjoint)
 
 
 def poisson_gaussian_sigma(y, gain, read_sigma):
@@ -844,23 +779,25 @@ class _NoiseMap:
         noise_map_path = noise_map_path or None
         if (noise_map is None) == (noise_map_path is None):
             raise ValueError(f"{name} needs exactly one of noise_map (an array) and noise_map_path (a .npy file)")
-        a = np.load(noise_map_path) if noise_map is None else \
-            (noise_map.detach().cpu().numpy() if torch.is_tensor(noise_map) else np.asarray(noise_map))
-        if tuple(a.shape) not in ((n, n), (3, n, n), (1, 3, n, n)):
-            raise ValueError(f"{name}: the noise map must have shape ({n}, {n}), (3, {n}, {n}) or (1, 3, {n}, {n}), got "
-                             f"{tuple(a.shape)}")
-        a = np.asarray(a, dtype=np.float64)
+        a = _load_array(name, "the noise map", noise_map, noise_map_path, _image_shapes(n))
+        self._set_noise_levels(np.ones((3, n, n)) * a.reshape((1, n, n) if a.ndim == 2 else (3, n, n)))
+
+    def _set_noise_levels(self, a, sites=None):
+        """`noise_map`, `weights` and `mask`, float64 [1, C, n, n], from a [C, n, n] array of standard deviations after the
+        checks and the floor; `sites` (boolean, the same shape): the entries that are sampled at all, inf elsewhere"""
+        name = self.name
         if np.isnan(a).any():
             raise ValueError(f"{name}: the noise map has a NaN entry")
         if not (a > 0).all():
             raise ValueError(f"{name}: the noise map has an entry <= 0 (entries are standard deviations > 0, or +inf for a "
                              "pixel that was not measured)")
+        if sites is not None:
+            a = np.where(sites, a, np.inf)
         if np.isinf(a).all():
             raise ValueError(f"{name}: the noise map is all inf - no pixel is measured")
-        s = np.ones((1, 3, n, n)) * a.reshape((1, 1, n, n) if a.ndim == 2 else (1, 3, n, n))
-        s = np.where(np.isinf(s), s, np.maximum(s, self._NOISE_FLOOR))
+        s = np.where(np.isinf(a), a, np.maximum(a, self._NOISE_FLOOR))[None]
         w = np.where(np.isinf(s), 0.0, 1.0 / s)
-        self.noise_map = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)  # float64 [1,3,n,n]
+        self.noise_map = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)
         self.weights = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
         self.mask = (self.weights > 0).to(F64)
 
@@ -882,15 +819,6 @@ class WeightedBlurOperator(_NoiseMap, CustomBlurOperator):
         CustomBlurOperator.__init__(self, in_shape, sigma_s, device, kernel_path=kernel_path, kernel=kernel)
         self._set_noise_map(int(in_shape[-1]), noise_map, noise_map_path)
 
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.in_shape[-3:])
-        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`: A0^T (mask * v)"""
-        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
-
 
 @register_operator(name="weighted_sr")
 class WeightedSROperator(_NoiseMap, CustomSROperator):
@@ -903,15 +831,6 @@ class WeightedSROperator(_NoiseMap, CustomSROperator):
         CustomSROperator.__init__(self, in_shape, sigma_s, device, scale_factor=scale_factor, kernel_path=kernel_path,
                                   kernel=kernel)
         self._set_noise_map(int(in_shape[-1]) // self.scale_factor, noise_map, noise_map_path)
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.out_shape[-3:])
-        return self._conv(y * self.mask.to(y.dtype), stride=self.scale_factor, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`: A0^T (mask * v)"""
-        return self._conv(v * self.mask.to(v.dtype), stride=self.scale_factor, adjoint=True).to(v.dtype)
 
 
 BAYER_PATTERNS = ("rggb", "bggr", "grbg", "gbrg")
@@ -977,47 +896,13 @@ class WeightedBurstSROperator(_NoiseMap, BurstSROperator):
                 raise ValueError(f"{name}: {fs.size} frame_sigmas for {K} frames; give one noise level per frame")
             a = np.repeat(fs, 3)[:, None, None] * np.ones((3 * K, n, n))
         else:
-            a = np.load(noise_map_path) if noise_map is None else \
-                (noise_map.detach().cpu().numpy() if torch.is_tensor(noise_map) else np.asarray(noise_map))
             shapes = ((n, n), (3, n, n), (K, 3, n, n), (3 * K, n, n), (1, 3 * K, n, n))
-            if tuple(a.shape) not in shapes:
-                raise ValueError(f"{name}: the noise map must have shape " + ", ".join(str(s) for s in shapes[:-1]) +
-                                 f" or {shapes[-1]}, got {tuple(a.shape)}")
-            a = np.asarray(a, dtype=np.float64)
+            a = _load_array(name, "the noise map", noise_map, noise_map_path, shapes)
             if a.ndim == 2 or a.shape == (3, n, n):  # one map for every frame ((3, n, n) is also (3 K, n, n) at K = 1: the same)
                 a = np.broadcast_to(a.reshape((1, 1, n, n) if a.ndim == 2 else (1, 3, n, n)), (K, 3, n, n))
-            a = np.ascontiguousarray(a).reshape(3 * K, n, n)
         self.mosaic = mosaic
-        self._set_burst_noise_map(a)
-
-    def _set_burst_noise_map(self, a):
-        """`_set_noise_map`'s checks, floor and tensors for a [3 K, So, So] array of standard deviations (the mosaic applied)"""
-        name, K, n = self.name, self.nframes, self.out_shape[-1]
-        a = np.array(a, dtype=np.float64).reshape(3 * K, n, n)
-        if np.isnan(a).any():
-            raise ValueError(f"{name}: the noise map has a NaN entry")
-        if not (a > 0).all():
-            raise ValueError(f"{name}: the noise map has an entry <= 0 (entries are standard deviations > 0, or +inf for a "
-                             "pixel that was not measured)")
-        if self.mosaic is not None:
-            a = np.where(np.tile(bayer_sites(n, self.mosaic), (K, 1, 1)), a, np.inf)
-        if np.isinf(a).all():
-            raise ValueError(f"{name}: the noise map is all inf - no pixel is measured")
-        s = a.reshape(1, 3 * K, n, n)
-        s = np.where(np.isinf(s), s, np.maximum(s, self._NOISE_FLOOR))
-        w = np.where(np.isinf(s), 0.0, 1.0 / s)
-        self.noise_map = torch.from_numpy(np.ascontiguousarray(s)).to(self.device)  # float64 [1,3K,So,So]
-        self.weights = torch.from_numpy(np.ascontiguousarray(w)).to(self.device)
-        self.mask = (self.weights > 0).to(F64)
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.out_shape[-3:])
-        return self._conv(y * self.mask.to(y.dtype), adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`: A^T (mask * v)"""
-        return self._conv(v * self.mask.to(v.dtype), adjoint=True).to(v.dtype)
+        self._set_noise_levels(np.ascontiguousarray(a).reshape(3 * K, n, n),
+                               None if mosaic is None else np.tile(bayer_sites(n, mosaic), (K, 1, 1)))
 
 
 def folded_dct_hartley_bases(S, use_dct=True):
@@ -1156,7 +1041,7 @@ _HARTLEY_CACHE = {}
 
 
 @register_operator(name="fourier_sampling")
-class FourierSamplingOperator(_NoiseMap, LinearOperator):
+class FourierSamplingOperator(_NoiseMap, _ImageOperator):
     """Undersampled Fourier-domain measurement, y = M (H x + n): H the orthonormal 2-D discrete Hartley transform
     H x = Re F x - Im F x per channel - real, symmetric, self-inverse, and an exact re-expression of k-space data (a sample at k
     with iid complex noise is the two Hartley samples at k and -k with iid noise; `kspace_to_hartley` converts) - and M a 0/1
@@ -1185,10 +1070,7 @@ class FourierSamplingOperator(_NoiseMap, LinearOperator):
         if pattern is not None:
             a = kspace_mask(S, pattern, acceleration, center_fraction, seed)
         else:
-            a = np.load(mask_path) if mask is None else (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask))
-        if tuple(a.shape) not in ((S, S), (3, S, S), (1, 3, S, S)):
-            raise ValueError(f"{name}: the mask must have shape ({S}, {S}), (3, {S}, {S}) or (1, 3, {S}, {S}), got {tuple(a.shape)}")
-        a = np.asarray(a, dtype=np.float64)
+            a = _load_array(name, "the mask", mask, mask_path, _image_shapes(S))
         if not np.isin(a, (0.0, 1.0)).all():
             raise ValueError(f"{name}: the mask has an entry other than 0 and 1 (per-entry noise levels go in noise_map)")
         m = np.ones((1, 3, S, S)) * a.reshape((1, 1, S, S) if a.ndim == 2 else (1, 3, S, S))
@@ -1230,37 +1112,11 @@ class FourierSamplingOperator(_NoiseMap, LinearOperator):
             _HARTLEY_CACHE[key] = (torch.from_numpy(P).to(dev), torch.from_numpy(np.ascontiguousarray(P.T)).to(dev))
         return _HARTLEY_CACHE[key]
 
-    def _conv(self, x, stride=None, adjoint=False):
-        """H x of an NCHW tensor [N,3,S,S]; float64.  H is its own adjoint and nothing decimates: both arguments are ignored."""
+    def apply(self, x, adjoint=False, ctx=None):
+        """H x of an NCHW tensor [N,3,S,S]; float64.  H is its own adjoint: `adjoint` is ignored."""
         S = self.in_shape[-1]
-        x64 = x.detach().to(device=self.device, dtype=F64).contiguous()
-        N = x64.shape[0]
-        assert tuple(x64.shape[1:]) == (3, S, S), f"fourier_sampling: expected [N,3,{S},{S}], got {tuple(x64.shape)}"
-        ctx = self._ctx() if N == 1 else _lib.Context.get(S, 3 * N, 0, self.ctx_slot)
+        x64, _N, ctx = self._images(x, (3, S, S), ctx)
         return ctx.hartley2d(x64, torch.empty_like(x64), self.hartley_basis())
-
-    def forward(self, data, flatten=False, noiseless=False):
-        # ONE noise draw at the grid's shape, then the mask
-        y = self._noise(self._conv(data).to(data.dtype), noiseless)
-        self._last_y = y
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.in_shape[-3:])
-        return self._conv(y * self.mask.to(y.dtype)).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`: H (mask * v)"""
-        return self._conv(v * self.mask.to(v.dtype)).to(v.dtype)
-
-    def folded_bases(self):
-        return None
-
-    def folded_sr_bases(self):
-        return None
 
 
 def _cubic(x):
@@ -1289,6 +1145,8 @@ def resize_matrix(n_in, scale):
 
 @register_operator(name="super_resolution")
 class SuperResolutionOperator(LinearOperator):  # measurements.py:87-123
+    decimates = True
+
     def __init__(self, in_shape, scale_factor, sigma_s, device, **kwargs):
         self.device = torch.device(device)
         self.scale_factor = int(scale_factor)
@@ -1313,13 +1171,8 @@ class SuperResolutionOperator(LinearOperator):  # measurements.py:87-123
             return y, y.reshape(y.shape[0], -1)
         return y
 
-    def transpose(self, y, flatten=False):
-        if flatten:
-            y = y.reshape(y.shape[0], *self.out_shape[-3:])
-        return self._conv(y, stride=self.scale_factor, adjoint=True).to(y.dtype)
-
     def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward` (the antialiased bicubic Resizer), for DPS"""
+        """exact adjoint of the noiseless `forward` (the antialiased bicubic Resizer), for DPS; `transpose` is the solver's A^T"""
         R = self._R.to(v.dtype)
         return torch.einsum("oh,pw,ncop->nchw", R, R, v.to(self.device))
 
@@ -1334,6 +1187,10 @@ class InpaintingOperator(LinearOperator):  # measurements.py:204-246
         self.sigma_s = torch.Tensor([sigma_s]).to(self.device)
         self.in_shape = (1, 3, mask_opt["image_size"], mask_opt["image_size"])
         self.mask = self.generate_mask(mask_opt) if mask is None else mask.to(self.device)
+
+    def apply(self, x, adjoint=False, ctx=None):
+        """mask * x in float64 (A = A^T, no kernel: the solver forms this family's right-hand side itself)"""
+        return x.detach().to(device=self.device, dtype=F64) * self.mask.to(F64)
 
     def forward(self, data, flatten=False, noiseless=False):
         y = self._noise(data.clone(), noiseless) * self.mask.to(data.dtype)
@@ -1375,6 +1232,7 @@ class ColorizationOperator(LinearOperator):  # measurements.py:74-84 (A = mean o
     """y = sum_c w_c x_c + noise, one measurement plane per image.  `channel_weights` defaults to (1/3, 1/3, 1/3), the
     reference's `mean(dim=1)`; the weights are shared by every image of a lock-step batch.  Forward and adjoint run in
     float64 through fh_channel_mix."""
+    keeps_last_y = False
 
     def __init__(self, in_shape, sigma_s, device, channel_weights=None, **kwargs):
         self.device = torch.device(device)
@@ -1390,25 +1248,14 @@ class ColorizationOperator(LinearOperator):  # measurements.py:74-84 (A = mean o
             self._w = torch.tensor(self.channel_weights, dtype=F64, device=self.device)
         return self._w
 
-    def _mix(self, x, adjoint=False):
+    def apply(self, x, adjoint=False, ctx=None):
         """float64 channel mix of an NCHW tensor ([N,3,S,S] -> [N,1,S,S], or its adjoint); returns float64."""
         S = self.in_shape[-1]
         x64 = x.detach().to(device=self.device, dtype=F64).reshape(-1, 1 if adjoint else 3, S, S).contiguous()
         out = torch.empty(x64.shape[0], 3 if adjoint else 1, S, S, dtype=F64, device=self.device)
-        return self._ctx().channel_mix(x64, out, self.weights, adjoint)
+        return (self._ctx() if ctx is None else ctx).channel_mix(x64, out, self.weights, adjoint)
 
-    def forward(self, data, flatten=False, noiseless=False):
-        y = self._noise(self._mix(data).to(data.dtype), noiseless)
-        if flatten:
-            return y, y.reshape(y.shape[0], -1)
-        return y
-
-    def transpose(self, y, flatten=False):
-        return self._mix(y, adjoint=True).to(y.dtype)
-
-    def forward_adjoint(self, v):
-        """exact adjoint of the noiseless `forward`, for DPS"""
-        return self._mix(v, adjoint=True).to(v.dtype)
+    _mix = apply
 
 
 @register_operator(name="noise")
@@ -1423,6 +1270,8 @@ class DenoiseOperator(LinearOperator):  # measurements.py:56-72 (A = I)
         self.in_shape = in_shape
         self.out_shape = tuple(in_shape)
         self.mask = torch.ones(1, *in_shape[-3:], device=self.device)
+
+    apply = InpaintingOperator.apply  # (the all-ones mask)
 
     def forward(self, data, flatten=False, noiseless=False):
         y = self._noise(data.clone(), noiseless)

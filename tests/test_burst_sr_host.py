@@ -191,8 +191,9 @@ def test_shifted_psf_fractional_part_is_bilinear_and_keeps_the_sum():
 # ---------------------------------------------------------------- solver tables and the CLI
 def test_op_code_and_name_lists():
     from free_hunch_amd import conditioning_mechanisms as cm
-    assert cm._OP_CODE["burst_sr"] == 12 and "burst_sr" in cm._DECIMATING and "'burst_sr'" in cm._BAD_OPERATOR
-    assert "burst_sr" not in cm._MASKED and "burst_sr" not in cm._WEIGHTED
+    row = cm._OPS["burst_sr"]
+    assert cm._op_code("burst_sr") == row.op == 12 and row.decimating and "'burst_sr'" in cm._BAD_OPERATOR
+    assert row.layout != "mask" and row.unit_sigma != "always"  # neither a 0/1-mask operator nor a noise-map one
     for name in ("gaussian_blur", "custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr"):
         assert f"'{name}'" in cm._BAD_OPERATOR  # the older names stay
     assert cm._sigma_y2(_burst()) == pytest.approx(0.05 ** 2)

@@ -51,10 +51,10 @@ def test_bad_channel_weights_are_rejected(bad):
 
 
 def test_solver_operator_codes():
-    from free_hunch_amd.conditioning_mechanisms import _OP_CODE, _sigma_y2
-    assert _OP_CODE["colorization"] == 3 and _OP_CODE["noise"] == 0
-    assert _OP_CODE["inpainting"] == 0 and _OP_CODE["gaussian_blur"] == 1 and _OP_CODE["motion_blur"] == 1
-    assert _OP_CODE["super_resolution"] == 2
+    from free_hunch_amd.conditioning_mechanisms import _op_code, _sigma_y2
+    assert _op_code("colorization") == 3 and _op_code("noise") == 0
+    assert _op_code("inpainting") == 0 and _op_code("gaussian_blur") == 1 and _op_code("motion_blur") == 1
+    assert _op_code("super_resolution") == 2
     # the clip(min=0.001) rule of blur and inpainting, in float32 like the reference
     assert _sigma_y2(_get("colorization")) == float(torch.tensor([0.05]).float().clip(min=0.001) ** 2)
     col0 = _get("colorization")

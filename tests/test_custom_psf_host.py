@@ -74,10 +74,11 @@ def test_a_psf_that_fills_half_its_window_gets_one():
 
 
 def test_super_resolution_keeps_the_tap_list_problem():
-    from free_hunch_amd.conditioning_mechanisms import _OP_CODE
+    from free_hunch_amd.conditioning_mechanisms import _OPS, _op_code
     from free_hunch_amd.measurements import get_operator
     sr = get_operator(name="super_resolution", device="cpu", sigma_s=0.05, in_shape=(1, 3, 64, 64), scale_factor=4)
-    assert _OP_CODE[sr.name] == 2 and sr.taps.n == 625  # dense, but op = 4 is emitted for blur operators only (_problem)
+    assert _op_code(sr.name) == 2 and sr.taps.n == 625  # dense, but op = 4 is emitted for blur operators only (_problem)
+    assert _OPS[sr.name].window is None and _OPS["custom_blur"].window == 4
 
 
 def test_sparse_psf_beyond_the_tile_kernels_lds_gets_a_window():
@@ -124,8 +125,8 @@ def test_kernel_and_kernel_path_exclude_each_other(tmp_path):
 
 
 def test_solver_names_the_operator():
-    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _OP_CODE, _sigma_y2
-    assert _OP_CODE["custom_blur"] == 1 and "custom_blur" in _BAD_OPERATOR
+    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _op_code, _sigma_y2
+    assert _op_code("custom_blur") == 1 and "custom_blur" in _BAD_OPERATOR
     assert _sigma_y2(_custom(kernel=disk_psf())) == float(torch.tensor([0.05]).float().clip(min=0.001) ** 2)
 
 

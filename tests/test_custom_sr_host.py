@@ -196,10 +196,10 @@ def test_rect_plan_rejects_bad_sizes(S, So, planes):
 
 
 def test_solver_names_the_operator():
-    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _OP_CODE, _SHARED_PSF, _sigma_y2
-    assert _OP_CODE["custom_sr"] == 2 == _OP_CODE["super_resolution"]
+    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _OPS, _op_code, _sigma_y2
+    assert _op_code("custom_sr") == 2 == _op_code("super_resolution")
     assert "custom_sr" in _BAD_OPERATOR and "custom_blur" in _BAD_OPERATOR and "masked_blur" in _BAD_OPERATOR
-    assert "custom_sr" in _SHARED_PSF
+    assert "share the PSF" in _OPS["custom_sr"].shares
     # the SR rule: sigma_s is clipped at 1e-2 before squaring
     from free_hunch_amd.measurements import get_operator
     small = get_operator(name="custom_sr", device="cpu", sigma_s=0.001, in_shape=(1, 3, 64, 64), scale_factor=4, kernel=box_psf(4))

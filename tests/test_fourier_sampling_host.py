@@ -235,9 +235,11 @@ def test_solver_tables():
     from free_hunch_amd import conditioning_mechanisms as cm
     name = "fourier_sampling"
     assert cm._op_code(name) == 15 and cm._op_code("varying_blur") == 14 and cm._op_code("noise") == 0 and cm._op_code("fourier") is None
-    assert name not in cm._OP_CODE and len(cm._OP_CODE) == 14 and cm._OP_CODE_MORE == {name: 15}
+    row = cm._OPS[name]
+    assert row.op == 15 and len(cm._OPS) == 15 and [n for n, r in cm._OPS.items() if r.op == 15] == [name]
     assert f"'{name}'" in cm._BAD_OPERATOR and cm._BAD_OPERATOR.rstrip(".").endswith("'varying_blur'")
-    assert all(name not in t for t in (cm._DECIMATING, cm._WEIGHTED, cm._BURST, cm._SHARED_PSF, cm._MASKED))
+    # not decimating, unit sigma only with a noise map, not the frames' layout, no shared PSF, no 0/1-mask operator
+    assert not row.decimating and row.unit_sigma == "noise_map" and row.layout == "hartley" and "share the PSF" not in row.shares
     op = _op()
     assert cm._solver_sigma_y2(op) == cm._sigma_y2(op) == pytest.approx(0.05 ** 2)
     tiny = _op()

@@ -133,8 +133,8 @@ def test_npy_mask_and_array_mask_give_equal_operators(tmp_path):
 
 
 def test_solver_names_the_operator():
-    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _OP_CODE, _sigma_y2
-    assert _OP_CODE["masked_blur"] == 5 and _OP_CODE["custom_blur"] == 1
+    from free_hunch_amd.conditioning_mechanisms import _BAD_OPERATOR, _op_code, _sigma_y2
+    assert _op_code("masked_blur") == 5 and _op_code("custom_blur") == 1
     assert "masked_blur" in _BAD_OPERATOR and "custom_blur" in _BAD_OPERATOR
     assert _sigma_y2(_masked(mask_border=1)) == float(torch.tensor([0.05]).float().clip(min=0.001) ** 2)  # the blur rule
 

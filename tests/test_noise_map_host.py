@@ -145,9 +145,10 @@ def test_poisson_gaussian_sigma_values():
 
 def test_op_code_tables():
     from free_hunch_amd import conditioning_mechanisms as cm
-    assert cm._OP_CODE["weighted_blur"] == 8 and cm._OP_CODE["weighted_sr"] == 10
-    assert {"weighted_blur", "weighted_sr"} <= set(cm._SHARED_PSF) and "weighted_sr" in cm._DECIMATING
-    assert "weighted_blur" not in cm._DECIMATING and not {"weighted_blur", "weighted_sr"} & set(cm._MASKED)
+    wb, ws = cm._OPS["weighted_blur"], cm._OPS["weighted_sr"]
+    assert cm._op_code("weighted_blur") == wb.op == 8 and cm._op_code("weighted_sr") == ws.op == 10
+    assert "share the PSF" in wb.shares and "share the PSF" in ws.shares and ws.decimating
+    assert not wb.decimating and wb.layout != "mask" and ws.layout != "mask"
     for name in ("gaussian_blur", "custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr"):
         assert f"'{name}'" in cm._BAD_OPERATOR
     assert cm._solver_sigma_y2(_wb(noise_map=np.full((S, S), 0.05))) == 1.0

@@ -231,12 +231,14 @@ def test_plan_refuses_illegal_arguments():
 def test_op_code_and_name_lists():
     from free_hunch_amd import conditioning_mechanisms as cm
     name = "varying_blur"
-    assert cm._OP_CODE[name] == 14
-    assert all(name not in t for t in (cm._DECIMATING, cm._WEIGHTED, cm._BURST, cm._SHARED_PSF, cm._MASKED))
+    row = cm._OPS[name]
+    assert cm._op_code(name) == row.op == 14
+    # not decimating, no noise map, not the frames' layout, no single shared PSF, no 0/1-mask operator
+    assert not row.decimating and row.unit_sigma != "always" and row.layout == "blend" and "share the PSF" not in row.shares
     older = {"inpainting": 0, "gaussian_blur": 1, "motion_blur": 1, "custom_blur": 1, "super_resolution": 2, "colorization": 3,
              "noise": 0, "masked_blur": 5, "custom_sr": 2, "weighted_blur": 8, "weighted_sr": 10, "burst_sr": 12,
              "weighted_burst_sr": 13}
-    assert {k: v for k, v in cm._OP_CODE.items() if k != name} == older
+    assert {k: cm._op_code(k) for k in older} == older and set(cm._OPS) == set(older) | {name, "fourier_sampling"}
     assert cm._BAD_OPERATOR.rstrip(".").endswith("'varying_blur'") and all(f"'{k}'" in cm._BAD_OPERATOR for k in older)
     op = _vb()
     assert cm._solver_sigma_y2(op) == cm._sigma_y2(op) == pytest.approx(0.05 ** 2)  # the blur rule: no 1e-2 clip ...

@@ -162,8 +162,9 @@ def test_mosaic_composes_with_each_source(tmp_path):
 def test_op_code_and_name_lists():
     from free_hunch_amd import conditioning_mechanisms as cm
     name = "weighted_burst_sr"
-    assert cm._OP_CODE[name] == 13 and name in cm._DECIMATING and name in cm._WEIGHTED and name in cm._BURST
-    assert name not in cm._SHARED_PSF and name not in cm._MASKED and "burst_sr" not in cm._WEIGHTED
+    row = cm._OPS[name]
+    assert cm._op_code(name) == row.op == 13 and row.decimating and row.unit_sigma == "always" and row.layout == "frames"
+    assert "share the PSF" not in row.shares and row.layout != "mask" and cm._OPS["burst_sr"].unit_sigma != "always"
     for older in ("gaussian_blur", "custom_blur", "masked_blur", "custom_sr", "weighted_blur", "weighted_sr", "burst_sr", name):
         assert f"'{older}'" in cm._BAD_OPERATOR
     op = _wb(frame_sigmas=[0.1] * 4)
