@@ -149,6 +149,8 @@ _SIGS = {
     "fh_noisy_u8": ([c_dp, C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, c_dp, C.c_void_p], C.c_int),
     "fh_sqerr_u8_scratch_doubles": ([C.c_int, C.c_int], C.c_int64),
     "fh_sqerr_u8": ([c_dp, c_dp, C.c_int, C.c_int, c_dp, c_dp, C.c_void_p], C.c_int),
+    "fh_ensemble_scratch_doubles": ([C.c_int, C.c_int], C.c_int64),
+    "fh_ensemble_stats": ([c_dp, c_dp, C.c_int, C.c_int, C.c_int, c_dp, c_dp, c_dp, c_dp, C.c_void_p], C.c_int),
     "fh_cg_solve_batched": ([C.c_void_p, C.POINTER(FhProblem), C.POINTER(FhBatch), c_dp, c_dp, C.POINTER(C.c_double),
                              C.c_double, C.c_int, C.POINTER(FhCgInfo), C.c_void_p], C.c_int),
     "fh_cg_solve": ([C.c_void_p, C.POINTER(FhProblem), c_dp, c_dp, C.c_double, C.c_double, C.c_int,

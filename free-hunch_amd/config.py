@@ -77,6 +77,11 @@ SCHEMA = {
     # measurements.kspace_mask); --noise_map_path optionally gives the noise level per frequency (inf = not measured)
     "kspace_pattern": (str, ""), "kspace_acceleration": (float, None), "kspace_center_fraction": (float, None),
     "kspace_seed": (int, None),
+    # NEW: K posterior samples per (image, seed) unit, 1 .. 64 (free_hunch_amd/ensemble.py): the K members share the operator's
+    # random content and ONE measurement and differ in their initial noise alone.  K >= 2 adds posterior_samples/, posterior_mean/
+    # (the MMSE estimate), posterior_std/ (.npy in 8-bit units, .png at 4 x) and the calibration lines of results.txt; images/
+    # keeps member 0, which is the run without the flag
+    "posterior_samples": (int, 1),
 }
 
 
@@ -100,6 +105,8 @@ def load_config(argv=None):
         cfg[key] = _coerce(SCHEMA[key][0], value) if key in SCHEMA else value
     if cfg["outdir"] is None:
         raise SystemExit("--outdir=DIR is required")
+    if not 1 <= cfg["posterior_samples"] <= 64:
+        raise SystemExit(f"--posterior_samples is the number of samples per measurement, 1 .. 64; got {cfg['posterior_samples']}")
     if bool(cfg["lpips_vgg_path"]) != bool(cfg["lpips_lin_path"]):
         raise SystemExit("--lpips_vgg_path and --lpips_lin_path go together: LPIPS needs both weight files")
     if cfg["operator_name"] == "custom_blur" and not cfg["kernel_path"]:

@@ -10,7 +10,9 @@ barrier, each rank runs `max_batch_size` images in lock-step, outputs are exchan
 RNG is keyed by (seed, image index).  PSNR, SSIM and LPIPS are computed on the device; LPIPS needs the two published weight
 files, which are not shipped: `--lpips_vgg_path=vgg16-397923af.pth --lpips_lin_path=weights/v0.1/vgg.pth` adds the `LPIPS:`
 line to results.txt, without them the run reports PSNR and SSIM only.
-`--synthetic_weights=ffhq|imagenet` runs with seeded random weights when no checkpoint is present."""
+`--synthetic_weights=ffhq|imagenet` runs with seeded random weights when no checkpoint is present.
+`--posterior_samples=K` draws K samples of the SAME measurement per (image, seed): posterior_samples/, posterior_mean/,
+posterior_std/ and the calibration lines of results.txt (free-hunch_amd/ensemble.py); images/ keeps member 0."""
 import os
 import sys
 
@@ -23,12 +25,11 @@ sys.path.insert(0, ROOT)
 
 
 def main(argv=None):
-    from free_hunch_amd import unet as hu
+    from free_hunch_amd import ensemble as ens, unet as hu
     from free_hunch_amd.config import load_config
-    from free_hunch_amd.measurements import get_operator, poisson_gaussian_sigma
     from free_hunch_amd.pipeline import gather_images, list_images, load_image_u8, lpips_u8, metrics_u8, shard_indices
     from free_hunch_amd.precond import iDDPMLinearPrecond
-    from free_hunch_amd.sampler import StandardRGBEncoder, conditional_sampler, conditional_sampler_grouped
+    from free_hunch_amd.sampler import StandardRGBEncoder
 
     o = load_config(argv)
     # LPIPS weights are read before anything else happens: a wrong path must not cost a sampling run
@@ -98,71 +99,48 @@ def main(argv=None):
                 discretization=o.discretization, schedule=o.schedule, scaling=o.scaling)
     churn = dict(S_churn=o.S_churn, S_min=o.S_min, S_max=o.S_max, S_noise=o.S_noise)
     # the lock-step sampler covers the deterministic loop; stochastic churn runs image by image like the reference
-    lockstep = o.conditioning_mechanism == "online_covariance" and o.S_churn == 0
+    # (ensemble.sample_batch chooses).  one unit = (image, seed): the reference repeats every image once per seed
+    # (generate_conditional.py:378-390); with --posterior_samples=K a unit has K adjacent members that share its measurement
+    K = o.posterior_samples
     outs, conds, fwds = [], [], []
-    # one unit = (image, seed): the reference repeats every image once per seed (generate_conditional.py:378-390)
-    units = [(i, sd) for i in mine for sd in o.seeds]
+    units = ens.list_units(mine, o.seeds, K)
+    stem = lambda i, sd: f"{i:06d}_{sd:06d}"
+    import PIL.Image
+    save_rgb = lambda u8, *path: PIL.Image.fromarray(u8.permute(1, 2, 0).cpu().numpy(), "RGB").save(os.path.join(o.outdir, *path))
+    if K > 1:
+        for sub in ("posterior_samples", "posterior_mean", "posterior_std"):
+            os.makedirs(os.path.join(o.outdir, sub), exist_ok=True)
+    members, means, calib, carry = [], [], [], None  # the open unit's samples; per finished unit: mean image, calibration sums
     for s in range(0, len(units), max(1, o.max_batch_size)):
         chunk = units[s: s + max(1, o.max_batch_size)]
-        ops, ys, noise, imgs = [], [], [], []
-        for b, (i, sd) in enumerate(chunk):
-            key = (sd * 1000003 + i) % (1 << 31)  # RNG keyed by (seed, image index): independent of the world size
-            np.random.seed(key)
-            torch.manual_seed(key)
-            op_kw = dict(device=device, sigma_s=o.noise_sigma, kernel_size=o.kernel_size, intensity=o.intensity,
-                         scale_factor=o.scale_factor, in_shape=(1, 3, S, S), kernel_path=o.kernel_path or None,
-                         mask_path=o.mask_path or None, mask_border=o.mask_border, frame_shifts=o.frame_shifts or None,
-                         frame_sigmas=o.frame_sigmas or None, mosaic=o.mosaic or None,
-                         blend_path=o.blend_path or None, psf_grid=o.psf_grid or None,
-                         pattern=o.kspace_pattern or None, acceleration=o.kspace_acceleration,
-                         center_fraction=0.08 if o.kspace_center_fraction is None else o.kspace_center_fraction,
-                         seed=0 if o.kspace_seed is None else o.kspace_seed,
-                         mask_opt={"mask_type": o.inpainting_type, "mask_len_range": (64, 156),
-                                   "mask_prob_range": (o.inpainting_prob_lower, o.inpainting_prob_upper)
-                                   if o.inpainting_type == "random" else (0.1, 0.3), "image_size": S})
-            img = load_image_u8(files[i], S)
-            x_true = enc.encode(img[None].to(device))
-            clean_name = {"weighted_blur": "custom_blur", "weighted_sr": "custom_sr", "weighted_burst_sr": "burst_sr"}
-            if o.operator_name in clean_name and o.noise_gain is not None:
-                # a Poisson-Gaussian sensor: the measurement is synthesised here with the noise level of the clean signal A0 x,
-                # and the solver gets the map estimated from the measurement itself - what a user with real data would have
-                clean = get_operator(name=clean_name[o.operator_name], **op_kw)
-                clean.ctx_slot = b
-                ax = clean.forward(x_true, noiseless=True)
-                y = ax + poisson_gaussian_sigma(ax, o.noise_gain, o.noise_read_sigma) * torch.randn_like(ax)
-                op = get_operator(name=o.operator_name, noise_map=poisson_gaussian_sigma(y, o.noise_gain, o.noise_read_sigma),
-                                  **op_kw)
-                y = y * op.mask.to(y.dtype)  # (all ones without a mosaic: a raw frame reads 0 off its pattern)
-            else:
-                op = get_operator(name=o.operator_name, noise_map_path=o.noise_map_path or None, **op_kw)
-                y = None
-            op.ctx_slot = b
-            imgs.append(img)
-            ops.append(op)
-            ys.append(op.forward(x_true, noiseless=False) if y is None else y)
-            noise.append(torch.randn((1, 3, S, S), generator=torch.Generator().manual_seed(key), dtype=torch.float32))
-        if lockstep:
-            # two lock-step groups per GPU from 4 images on (the Free Hunch phase of one overlaps the UNet phase of the other:
-            # +7 % at batch 8 on MI355X); FH_LOCKSTEP_GROUPS=1 runs the batch as one group
-            ng = int(os.environ.get("FH_LOCKSTEP_GROUPS", "2")) if len(ops) >= 4 else 1
-            x = conditional_sampler_grouped(net, torch.cat(noise).to(device), ys, ops, groups=ng, **loop, **kw)
-        else:  # comparison methods and churned runs go image by image (batch 1, as in the reference)
-            gens = [torch.Generator(device).manual_seed((sd * 1000003 + i) % (1 << 31)) for i, sd in chunk]
-            x = torch.cat([conditional_sampler(
-                net, noise[b].to(device), None, None, **loop, **churn, measurement=ys[b], operator=ops[b],
-                randn_like=lambda t, g=gens[b]: torch.randn(t.shape, generator=g, dtype=t.dtype, device=t.device),
-                **kw)[0].detach() for b in range(len(ops))])
-        outs.append(enc.decode(x))
-        conds.append(torch.stack(imgs).to(device))
+        ops, ys, noise, imgs, carry = ens.build_batch(o, files, chunk, S, device, carry)
+        x = ens.sample_batch(net, ops, ys, noise, churn_seeds=[ens.member_seed(ens.unit_key(i, sd), k) for i, sd, k in chunk],
+                             **loop, **churn, **kw)
+        first = [b for b, u in enumerate(chunk) if u[2] == 0]  # member 0 is the run without the flag: images/, the metrics
+        if first:
+            outs.append(enc.decode(x[first]))
+            conds.append(torch.stack([imgs[b] for b in first]).to(device))
         if o.operator_name == "fourier_sampling":  # a frequency grid is no picture: the zero-filled reconstruction A0^T y
-            fwds += [enc.decode(op.transpose(y)) for op, y in zip(ops, ys)]
+            fwds += [enc.decode(ops[b].transpose(ys[b])) for b in first]
         else:
-            fwds += [enc.decode(y) for y in ys]
-        print(f"[rank {rank}] (image, seed) {chunk} done", flush=True)
+            fwds += [enc.decode(ys[b]) for b in first]
+        for b, (i, sd, k) in enumerate(chunk) if K > 1 else ():
+            # the samples stay on this rank: PNG per member, and the unit's statistics once its last member is in
+            save_rgb(enc.decode(x[b]), "posterior_samples", f"{stem(i, sd)}_{k:03d}.png")
+            members.append(x[b])
+            if k == K - 1:
+                st = ens.ensemble_stats(torch.stack(members), imgs[b].to(device))
+                members = []
+                means.append(st.mean_u8)
+                calib.append(torch.stack([st.spread2, st.skill2, st.cover1, st.cover2]))
+                save_rgb(st.mean_u8, "posterior_mean", stem(i, sd) + ".png")
+                np.save(os.path.join(o.outdir, "posterior_std", stem(i, sd) + ".npy"), st.std.cpu().numpy())
+                save_rgb((4.0 * st.std).round().clamp(max=255).to(torch.uint8), "posterior_std", stem(i, sd) + ".png")
+        print(f"[rank {rank}] (image, seed) {[u[:2] for u in chunk] if K == 1 else chunk} done", flush=True)
     local_out = torch.cat(outs) if outs else torch.zeros((0, 3, S, S), dtype=torch.uint8, device=device)
     local_cond = torch.cat(conds) if conds else torch.zeros((0, 3, S, S), dtype=torch.uint8, device=device)
     ns = len(o.seeds)
-    unit_ids = [i * ns + o.seeds.index(sd) for i, sd in units]  # global position of (image, seed)
+    unit_ids = [i * ns + o.seeds.index(sd) for i, sd, k in units if k == 0]  # global position of (image, seed)
     # metrics as in generate_conditional.py:539-569: per image on the device (fh_metrics_u8); the partial sums travel in the
     # header of the ONE all_gather that collects the images (the reference: a barrier per image + three all_reduces)
     sums = torch.zeros(3 if lpips_state is None else 4, dtype=torch.float64, device=device)
@@ -172,14 +150,35 @@ def main(argv=None):
         if lpips_state is not None:  # fourth header element: the rank-local LPIPS sum
             parts.append(lpips_u8(local_out, local_cond, lpips_model).sum())
         sums = torch.stack(parts)
+    nbase = sums.numel()
+    if K > 1:
+        # the ensembles' sums ride in the same header: the samples themselves do not travel.  Per rank: PSNR and SSIM (and LPIPS)
+        # of the mean images, then spread^2, skill^2 and the two covered fractions, each summed over this rank's units
+        post = torch.zeros(nbase + 3, dtype=torch.float64, device=device)
+        if means:
+            mean_imgs = torch.stack(means)
+            ps, ss = metrics_u8(mean_imgs, local_cond)
+            parts = [ps.sum(), ss.sum()]
+            if lpips_state is not None:
+                parts.append(lpips_u8(mean_imgs, local_cond, lpips_model).sum())
+            post = torch.cat([torch.stack(parts), torch.stack(calib).sum(0)])
+        sums = torch.cat([sums, post])
     all_out, sums = gather_images(local_out, unit_ids, total * ns, device, partial_sums=sums)  # the single exchange of the run
     psnr_mean, ssim_mean = float(sums[0] / sums[2]), float(sums[1] / sums[2])
     lpips_line = lpips_print = ""
     if lpips_state is not None:
         lpips_mean = float(sums[3] / sums[2])
         lpips_line, lpips_print = f"LPIPS: {lpips_mean:.4f}\n", f", LPIPS {lpips_mean:.4f}"
+    post_lines = ""
+    if K > 1:
+        pm = [float(v / sums[2]) for v in sums[nbase:]]  # means over the units
+        spread2, skill2, cover1, cover2 = pm[-4:]
+        ratio = ((1 + 1 / K) * spread2 / skill2) ** 0.5 if skill2 > 0 else float("inf")
+        post_lines = (f"posterior_samples: {K}\nPSNR(mean): {pm[0]:.4f}\nSSIM(mean): {pm[1]:.4f}\n"
+                      + (f"LPIPS(mean): {pm[2]:.4f}\n" if lpips_state is not None else "")
+                      + f"spread: {spread2 ** 0.5:.4f}\nskill: {skill2 ** 0.5:.4f}\nspread/skill: {ratio:.4f}\n"
+                      f"coverage(1 sigma): {cover1:.4f}\ncoverage(2 sigma): {cover2:.4f}\n")
     name = lambda u: f"{u // ns:06d}_{o.seeds[u % ns]:06d}.png"
-    import PIL.Image
     for sub in ("images", "cond_images", "forward_images"):
         os.makedirs(os.path.join(o.outdir, sub), exist_ok=True)
     if rank == 0:
@@ -190,8 +189,11 @@ def main(argv=None):
                 PIL.Image.fromarray(load_image_u8(files[u // ns], S).permute(1, 2, 0).numpy(), "RGB").save(
                     os.path.join(o.outdir, "cond_images", name(u)))
         with open(os.path.join(o.outdir, "results.txt"), "w") as f:
-            f.write(f"PSNR: {psnr_mean:.4f}\nSSIM: {ssim_mean:.4f}\n{lpips_line}images: {total * ns}\n")
+            f.write(f"PSNR: {psnr_mean:.4f}\nSSIM: {ssim_mean:.4f}\n{lpips_line}images: {total * ns}\n{post_lines}")
         print(f"PSNR {psnr_mean:.3f} dB, SSIM {ssim_mean:.4f}{lpips_print} over {total * ns} images -> {o.outdir}", flush=True)
+        if K > 1:
+            print(f"posterior ensembles of {K}: PSNR(mean) {pm[0]:.3f} dB, spread/skill {ratio:.3f}, coverage "
+                  f"{cover1:.3f} / {cover2:.3f} at 1 / 2 sigma", flush=True)
     for j, u in enumerate(unit_ids):  # forward (measurement) images are written by the owning rank
         if fwds[j].shape[-1] == S and fwds[j].shape[1] == 1:  # a one-channel measurement (colorization): 8-bit grayscale
             PIL.Image.fromarray(fwds[j][0, 0].cpu().numpy(), "L").save(os.path.join(o.outdir, "forward_images", name(u)))

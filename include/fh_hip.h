@@ -740,6 +740,23 @@ int fh_noisy_u8(const uint8_t* imgs, const int64_t* img_index, int n, int S, dou
 int64_t fh_sqerr_u8_scratch_doubles(int n, int S);
 int fh_sqerr_u8(const float* D, const uint8_t* imgs, int n, int S, double* scratch, double* out, void* stream);
 
+/* Posterior ensembles (free-hunch_amd/ensemble.py): N ensembles of K samples of one measurement each, n = C*H*W elements per
+ * image.  x [N][K][n] float64 in the sampler's units ([-1, 1]); truth [N][n] uint8 or NULL.  Per element, in 8-bit units and
+ * without contraction:  v_k = min(max(127.5 x_k + 127.5, 0), 255),  m = (((v_0 + v_1) + v_2) + ...) / K,
+ * SS = sum_k (v_k - m)^2 (second pass, member order),  mean_u8 = (uint8) floor(m + 0.5),  std = (float) sqrt(SS / (K - 1)).
+ * With d2 = (truth - m)^2 the element is covered at c sigma when d2 K (K - 1) <= c^2 SS (K + 1): the truth is judged as a
+ * (K + 1)-th draw, whose variance about the ensemble mean is s^2 (1 + 1/K).
+ *   out [N][4] = mean over the elements of SS / (K - 1) (spread^2), mean of d2 (skill^2), covered fraction at c = 1, at c = 2;
+ *   the last three are -1 with truth == NULL.
+ * One workgroup per fixed chunk of one ensemble writes its partials, a second kernel adds an ensemble's chunks in index order:
+ * no atomics, the chunking depends on n alone, so every output of an ensemble is bitwise the same at any N and in any slot.
+ * Members are read 16 bytes at a time when n is even and x is 16-byte aligned, else element by element: same values.
+ * FH_EINVAL before any launch: a null x, mean_u8, std, scratch or out; N < 1; n < 1; K < 2; K > 64.  FH_ESIZE: N > 65535.
+ * scratch: fh_ensemble_scratch_doubles(N, n) doubles (0 for N < 1 or n < 1). */
+int64_t fh_ensemble_scratch_doubles(int N, int n);
+int fh_ensemble_stats(const double* x, const uint8_t* truth, int N, int K, int n, uint8_t* mean_u8, float* std, double* scratch,
+                      double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
